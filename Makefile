@@ -19,7 +19,7 @@ test-gpu:
 	$(PYTHON) -m pytest tests/ -x -q -m gpu
 
 bench:
-	$(PYTHON) bench.py --steps 20 --warmup 5
+	$(PYTHON) bench.py --steps 20 --warmup 5 --full
 
 # Regenerate CRD manifests (controller-gen analog); CI asserts no drift.
 manifests:

@@ -22,8 +22,9 @@ rule 3, composabilityrequest_webhook.go:107-128) rejects duplicate
 node are inadmissible BY DESIGN; the per-device fan-out happens inside
 one CR.  Cross-node pool contention is measured separately (below).
 
-After the timed region, secondary configs run once and are reported as
-extra keys:
+A plain run sets up, warms up, times the N steps and prints the result
+line.  With ``--full`` the secondary configs also run once after the timed
+region and are reported as extra keys:
   single     — CR(size=1) cycles: the pure per-device overhead path
   churn      — 1→4→N→0 spec updates under the validating webhook
                (BASELINE config #4)
@@ -44,17 +45,202 @@ latency in ms for the size-N bulk compose (lower is better — the
 reference's implicit envelope is its 30 s visibility-poll quantum through
 ONE reconcile worker); ``reconciles_per_sec`` counts both
 controllers in the one shared process — the GIL-contention number.
+``ms_per_step`` is the wall time of one timed step (attach + detach).
+
+So that two runs can be compared, the timed region is kept free of two
+host effects that are not the operator's work.  The process confines
+itself to a fixed number of neighbouring CPUs (``--cpus K``; default one
+per GPU and at least 4, ``--cpus 0`` leaves the affinity alone), so the
+placement of its threads is the same from run to run; and the heap built
+during set-up and warm-up is frozen out of the garbage collector, so a
+full collection over it cannot land in a random timed step
+(``--gc-in-steps`` leaves the collector alone).  Objects the steps
+allocate are still collected.  ``config.cpus`` and ``config.gc_frozen``
+in the result line say what a run did.
+
+``--dump-outputs DIR`` writes what the LAST timed step computed as
+``DIR/<name>.npy`` (float64), so two builds can be compared output for
+output.  Only run-to-run deterministic results are written (what the
+request looked like when it reached Running, the health-probe verdicts,
+what was left after teardown) — never timings or measured rates:
+
+  request_status   [size asked, resources in status, state is Running,
+                    resources Online]
+  resources        one row per composed device, in inventory order:
+                   [state is Online, device id present and unlike every
+                    other row's, fabric CDI id present, on the target
+                    node, no error]
+  probe            one row per device probed in that step, same order:
+                   [ok, mfma_f32_exact, rc] (no rows on the mock node path)
+  probe_mfma_tile  one 16x16 tile per probed device, same order.  The step
+                   keeps only the probe's exactness flag, so the probe's
+                   f32 MFMA kernel is run once more after the timed steps
+                   on the probe's own inputs and its product written here
+  teardown         [request seen DELETED, CDI devices left on the node,
+                    fabric attachments left on the node]
 """
 
 from __future__ import annotations
 
 import argparse
+import gc
 import json
 import os
 import statistics
 import sys
 import threading
 import time
+
+
+class _RecordingEvents:
+    """Pass-through view of a request watch queue that remembers every
+    event its consumer took — what the caller of the final timed step saw."""
+
+    def __init__(self, inner):
+        self.inner = inner
+        self.seen = []
+
+    def get(self, timeout=None):
+        ev = self.inner.get(timeout=timeout)
+        self.seen.append(ev)
+        return ev
+
+
+def _probe_inputs():
+    """A(16x64) and B(64x16) exactly as the health probe builds them
+    (probe.hip: one LCG stream fills A, then B, with 24-bit fractions in
+    [-0.5, 0.5))."""
+    import numpy as np
+
+    K = 64
+    vals = np.empty(2 * 16 * K, dtype=np.float32)
+    s = 0x9E3779B9
+    for i in range(vals.size):
+        s = (s * 1664525 + 1013904223) & 0xFFFFFFFF
+        vals[i] = np.float32(s >> 8) / np.float32(16777216.0) - np.float32(0.5)
+    return vals[: 16 * K].reshape(16, K).copy(), vals[16 * K:].reshape(K, 16).copy()
+
+
+def _probe_mfma_tile(stack, device_id):
+    """D(16x16) = A @ B from the health probe's f32 MFMA kernel on the
+    probe's own inputs."""
+    import ctypes
+
+    import numpy as np
+
+    from cro_amd.nodeops.probe import hip_device_for_bdf, load_library
+
+    a, b = _probe_inputs()
+    K = a.shape[1]
+    d = np.zeros(256, dtype=np.float32)
+
+    gpu = stack.ops.find_gpu(stack.node_name, device_id)
+    dev = hip_device_for_bdf(gpu.pci_bdf) if gpu is not None else None
+    lib = load_library(required=True)
+    fptr = ctypes.POINTER(ctypes.c_float)
+    lib.cro_probe_mfma_f32.argtypes = [ctypes.c_int, fptr, fptr, fptr, ctypes.c_int]
+    lib.cro_probe_mfma_f32.restype = ctypes.c_int
+    rc = lib.cro_probe_mfma_f32(
+        dev or 0, a.ctypes.data_as(fptr), b.ctypes.data_as(fptr),
+        d.ctypes.data_as(fptr), K,
+    )
+    if rc != 0:
+        raise RuntimeError(f"f32 MFMA tile on {device_id} failed: rc={rc}")
+    return d.reshape(16, 16)
+
+
+def _step_outputs(stack, name, size, seen, probes) -> dict:
+    """The deterministic results of one attach→detach step as float64
+    arrays (layout in the module docstring)."""
+    import numpy as np
+
+    node = stack.node_name
+    # real devices in enumeration order; mock ids are random per run and
+    # sort after them by id
+    order = {did: i for i, did in enumerate(stack.device_ids)}
+
+    def rank(device_id):
+        return (order.get(device_id, len(order)), device_id)
+
+    running = None
+    deleted = False
+    for ev in seen:
+        if ev.object.metadata.name != name:
+            continue
+        if ev.type == "DELETED":
+            deleted = True
+        elif ev.object.status.state == "Running":
+            running = ev.object
+    children = []
+    if running is not None:
+        children = sorted(
+            running.status.resources.values(),
+            key=lambda r: rank(r.device_id),
+        )
+    ids = [r.device_id for r in children]
+    rows = [
+        [
+            float(r.state == "Online"),
+            float(bool(r.device_id) and ids.count(r.device_id) == 1),
+            float(bool(r.cdi_device_id)),
+            float(r.node_name == node),
+            float(not r.error),
+        ]
+        for r in children
+    ]
+    probe_rows = [
+        [float(bool(pr.get("ok"))), float(bool(pr.get("mfma_f32_exact"))),
+         float(pr.get("rc", 0))]
+        for _, pr in sorted(probes.items(), key=lambda kv: rank(kv[0]))
+    ]
+    tiles = [_probe_mfma_tile(stack, did) for did in sorted(probes, key=rank)]
+    if hasattr(stack.ops, "cdi"):
+        cdi_left = len(stack.ops.cdi.devices(node))
+    else:
+        cdi_left = len(stack.ops.cdi_written.get(node, ()))
+    return {
+        "request_status": np.array(
+            [
+                float(size),
+                float(len(children)),
+                float(running is not None),
+                float(sum(r.state == "Online" for r in children)),
+            ],
+            dtype=np.float64,
+        ),
+        "resources": np.array(rows, dtype=np.float64).reshape(len(rows), 5),
+        "probe": np.array(probe_rows, dtype=np.float64).reshape(len(probe_rows), 3),
+        "probe_mfma_tile": np.array(tiles, dtype=np.float64).reshape(len(tiles), 16, 16),
+        "teardown": np.array(
+            [float(deleted), float(cdi_left),
+             float(len(stack.fabric.attached_to(node)))],
+            dtype=np.float64,
+        ),
+    }
+
+
+def _confine_to_neighbouring_cpus(k: int) -> None:
+    """Restrict this process (and every thread it starts later) to the
+    aligned block of ``k`` allowed CPUs around the one it runs on now.
+
+    Where the scheduler puts the operator's threads on a large host
+    differs from run to run and shows in the step time; a fixed small set
+    of adjacent CPUs takes that difference away."""
+    if k <= 0 or not hasattr(os, "sched_setaffinity"):
+        return
+    allowed = sorted(os.sched_getaffinity(0))
+    if len(allowed) <= k:
+        return
+    here = allowed[0]
+    try:
+        with open("/proc/self/stat") as f:
+            # field 39 (processor); the comm field may itself hold spaces
+            here = int(f.read().rsplit(")", 1)[1].split()[36])
+    except (OSError, ValueError, IndexError):
+        pass
+    pos = allowed.index(here) if here in allowed else 0
+    start = min(pos - pos % k, len(allowed) - k)
+    os.sched_setaffinity(0, set(allowed[start:start + k]))
 
 
 def main() -> int:
@@ -70,8 +256,17 @@ def main() -> int:
     p.add_argument("--fabric-async", action="store_true",
                    help="CM-style asynchronous fabric (resize+poll) for the "
                    "main phase")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the single/churn/"
+                   "contention/async secondary configs and report them as "
+                   "extra keys (a plain run measures the headline only)")
     p.add_argument("--skip-extras", action="store_true",
-                   help="skip the single/churn/contention/async secondary configs")
+                   help="deprecated: a plain run no longer runs the "
+                   "secondary configs; accepted so older command lines "
+                   "keep working")
+    p.add_argument("--dump-outputs", metavar="DIR", default="",
+                   help="write what the last timed step computed as "
+                   "DIR/<name>.npy (float64)")
     p.add_argument(
         "--force-detach",
         action="store_true",
@@ -79,7 +274,23 @@ def main() -> int:
         "for test environments where another process legitimately holds a "
         "KFD context on the bench GPU)",
     )
+    p.add_argument("--cpus", type=int, default=None,
+                   help="confine the operator process to this many "
+                   "neighbouring CPUs so runs are comparable (default: one "
+                   "per GPU, at least 4; 0 = leave the CPU affinity alone)")
+    p.add_argument("--gc-in-steps", action="store_true",
+                   help="do not freeze the set-up heap out of the garbage "
+                   "collector before the timed steps")
     args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+
+    # before torch/HIP start their threads: they inherit the mask. Only the
+    # rank that runs the operator is confined.
+    if int(os.environ.get("RANK", "0")) == 0:
+        if args.cpus is None:
+            args.cpus = max(4, args.gpus, int(os.environ.get("WORLD_SIZE", "1")))
+        _confine_to_neighbouring_cpus(args.cpus)
 
     import torch
 
@@ -89,7 +300,13 @@ def main() -> int:
         import torch.distributed as dist_mod
 
         dist = dist_mod
-        backend = "nccl" if torch.cuda.is_available() else "gloo"
+        # NCCL needs a device per rank; with fewer, the ranks meet over gloo
+        backend = (
+            "nccl"
+            if torch.cuda.is_available()
+            and torch.cuda.device_count() >= int(os.environ["WORLD_SIZE"])
+            else "gloo"
+        )
         dist.init_process_group(backend=backend)
         rank = dist.get_rank()
         world = dist.get_world_size()
@@ -151,16 +368,40 @@ def main() -> int:
         # on CPU (the driver's --gpus N values 1/2/4/8 → CR size 1/2/4/8)
         size = len(stack.device_ids) if use_gpu else n_gpus
 
+        # keep the newest health-probe verdict per device (--dump-outputs)
+        last_probes: dict = {}
+        inner_probe = getattr(stack.ops, "probe_fn", None)
+        if inner_probe is not None:
+
+            def recording_probe(gpu):
+                res = inner_probe(gpu)
+                last_probes[gpu.device_id] = res
+                return res
+
+            stack.ops.probe_fn = recording_probe
+
         for i in range(args.warmup):  # HIP context + probe first-touch
             attach_detach_cycle(stack, f"warm-{i}", size=size,
                                 force_detach=args.force_detach)
+
+        # the final step's caller-side view of the request (--dump-outputs)
+        last_events = _RecordingEvents(stack.request_events)
+        last_step = args.steps - 1
+
+        # everything allocated so far (torch, the stack, warm-up leftovers)
+        # leaves the collector's sight: a full collection over that heap
+        # costs 100+ ms and would land in a random timed step
+        if not args.gc_in_steps:
+            gc.collect()
+            gc.freeze()
 
         barrier()
         rec0 = reconcile_count(stack)
         t_start = time.monotonic()
         samples = [
             attach_detach_cycle(stack, f"step-{i}", size=size,
-                                force_detach=args.force_detach)
+                                force_detach=args.force_detach,
+                                events=last_events if i == last_step else None)
             for i in range(args.steps)
         ]
         barrier()
@@ -168,6 +409,15 @@ def main() -> int:
         rec1 = reconcile_count(stack)
 
         elapsed = t_end - t_start
+        if args.dump_outputs:
+            import numpy as np
+
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            outputs = _step_outputs(
+                stack, f"step-{last_step}", size, last_events.seen, last_probes
+            )
+            for key, arr in outputs.items():
+                np.save(os.path.join(args.dump_outputs, f"{key}.npy"), arr)
         attach_ms = sorted(s["attach_ms"] for s in samples)
         detach_ms = sorted(s["detach_ms"] for s in samples)
 
@@ -189,7 +439,8 @@ def main() -> int:
                 json.dump(phases, f, indent=2)
 
         extras = {}
-        if not args.skip_extras:
+        run_extras = args.full and not args.skip_extras
+        if run_extras:
             # pure per-device overhead path (round-1 headline shape)
             singles = [
                 attach_detach_cycle(stack, f"single-{i}", size=1,
@@ -276,7 +527,7 @@ def main() -> int:
             }
         stack.mgr.stop()
 
-        if not args.skip_extras:
+        if run_extras:
             # async-compose config: CM-style resize+poll
             # fabric with a real RTT, own small stack so the headline and
             # the async number are separate records
@@ -347,6 +598,9 @@ def main() -> int:
                 "device_resource_type": args.mode,
                 "probe": bool(use_gpu and not args.no_probe),
                 "force_detach": bool(args.force_detach),
+                "cpus": (len(os.sched_getaffinity(0))
+                         if hasattr(os, "sched_getaffinity") else None),
+                "gc_frozen": not args.gc_in_steps,
             },
             **extras,
         }
