@@ -11,6 +11,8 @@
 //   croagent cxl    [--sysroot /]            CXL.mem inventory (/sys/bus/cxl)
 //   croagent pids   [--gpu-id N]             KFD compute processes
 //   croagent probe  [--device N | --bdf B]   gfx950 MFMA/HBM health probe
+//       [--deep [--vram-mib N] [--link-mib N] [--link-floor-gbps X]]
+//                                            + VRAM / host-link data integrity
 //   croagent drain  --bdf 0000:5a:00.0       sysfs PCI remove
 //   croagent rescan                          sysfs PCI rescan
 //
@@ -271,6 +273,56 @@ int resolve_device_by_bdf(const std::string& bdf) {
   return -1;
 }
 
+void print_integrity(const CroIntegrityResult& r) {
+  printf("\"integrity\":{\"ok\":%s,\"rc\":%d,\"n_bad\":%llu,\"first_bad_byte\":%llu,"
+         "\"bits_bad\":%u,\"failed_stage\":\"%s\",\"vram_passes\":%d,\"link_passes\":%d,"
+         "\"vram_chunks\":%d,",
+         r.ok ? "true" : "false", r.rc, r.n_bad, r.first_bad_byte, r.bits_bad,
+         r.failed_stage, r.vram_passes, r.link_passes, r.vram_chunks);
+  printf("\"vram_bytes_verified\":%lld,\"h2d_dma_bytes_verified\":%lld,"
+         "\"d2h_dma_bytes_verified\":%lld,\"h2d_kernel_bytes_verified\":%lld,"
+         "\"d2h_kernel_bytes_verified\":%lld,",
+         r.vram_bytes_verified, r.h2d_dma_bytes_verified, r.d2h_dma_bytes_verified,
+         r.h2d_kernel_bytes_verified, r.d2h_kernel_bytes_verified);
+  printf("\"vram_n_bad\":%llu,\"h2d_dma_n_bad\":%llu,\"d2h_dma_n_bad\":%llu,"
+         "\"h2d_kernel_n_bad\":%llu,\"d2h_kernel_n_bad\":%llu,",
+         r.vram_n_bad, r.h2d_dma_n_bad, r.d2h_dma_n_bad, r.h2d_kernel_n_bad,
+         r.d2h_kernel_n_bad);
+  printf("\"vram_fill_gbps\":%.1f,\"vram_verify_gbps\":%.1f,\"h2d_dma_gbps\":%.1f,"
+         "\"d2h_dma_gbps\":%.1f,\"h2d_kernel_gbps\":%.1f,\"d2h_kernel_gbps\":%.1f,",
+         r.vram_fill_gbps, r.vram_verify_gbps, r.h2d_dma_gbps, r.d2h_dma_gbps,
+         r.h2d_kernel_gbps, r.d2h_kernel_gbps);
+  printf("\"t_vram_ms\":%.1f,\"t_link_dma_ms\":%.1f,\"t_link_kernel_ms\":%.1f,"
+         "\"t_total_ms\":%.1f,\"msg\":\"%s\"}",
+         r.t_vram_ms, r.t_link_dma_ms, r.t_link_kernel_ms, r.t_total_ms, r.msg);
+}
+
+// --deep: the quick probe first; a device that failed it is not stressed
+// further.  Top-level "ok" and "msg" then cover both stages.
+int cmd_probe_deep(int device, const CroIntegrityOpts& opts) {
+  CroProbeResult result;
+  int rc = cro_probe_run(device, &result);
+  CroIntegrityResult integ;
+  bool ran = false;
+  if (result.ok) {
+    cro_probe_integrity(device, &opts, &integ);
+    ran = true;
+  }
+  bool ok = result.ok && ran && integ.ok;
+  printf("{\"ok\":%s,\"rc\":%d,\"mfma_f32_exact\":%s,\"hbm_gbps\":%.1f,"
+         "\"bf16_tflops\":%.1f,\"vram_total\":%lld,\"vram_free\":%lld,"
+         "\"gcn_arch\":\"%s\",\"msg\":\"%s\"",
+         ok ? "true" : "false", rc, result.mfma_f32_exact ? "true" : "false",
+         result.hbm_gbps, result.bf16_tflops, result.vram_total, result.vram_free,
+         result.gcn_arch, (ran && !integ.ok) ? integ.msg : result.msg);
+  if (ran) {
+    printf(",");
+    print_integrity(integ);
+  }
+  printf("}\n");
+  return ok ? 0 : 1;
+}
+
 int cmd_probe(int device) {
   CroProbeResult result;
   int rc = cro_probe_run(device, &result);
@@ -294,12 +346,19 @@ int main(int argc, char** argv) {
   std::string bdf;
   long long gpu_id = -1;
   int device = 0;
+  bool deep = false;
+  CroIntegrityOpts integ_opts;
+  memset(&integ_opts, 0, sizeof(integ_opts));
   for (int i = 2; i < argc; ++i) {
     std::string arg = argv[i];
     if (arg == "--sysroot" && i + 1 < argc) g_sysroot = argv[++i];
     else if (arg == "--bdf" && i + 1 < argc) bdf = argv[++i];
     else if (arg == "--gpu-id" && i + 1 < argc) gpu_id = atoll(argv[++i]);
     else if (arg == "--device" && i + 1 < argc) device = atoi(argv[++i]);
+    else if (arg == "--deep") deep = true;
+    else if (arg == "--vram-mib" && i + 1 < argc) integ_opts.vram_bytes = atoll(argv[++i]) << 20;
+    else if (arg == "--link-mib" && i + 1 < argc) integ_opts.link_bytes = atoll(argv[++i]) << 20;
+    else if (arg == "--link-floor-gbps" && i + 1 < argc) integ_opts.link_floor_gbps = atof(argv[++i]);
   }
   if (cmd == "list") return cmd_list();
   if (cmd == "cxl") return cmd_cxl();
@@ -314,7 +373,7 @@ int main(int argc, char** argv) {
         return 1;
       }
     }
-    return cmd_probe(device);
+    return deep ? cmd_probe_deep(device, integ_opts) : cmd_probe(device);
   }
   if (cmd == "drain") return cmd_drain(bdf);
   if (cmd == "rescan") return cmd_rescan();

@@ -46,6 +46,40 @@ def parse_port(addr: str, default: int) -> int:
     return int(addr.rsplit(":", 1)[-1])
 
 
+def add_probe_arguments(p: argparse.ArgumentParser) -> None:
+    """Health-probe level and the deep level's sizes (env defaults are read
+    when the parser is built)."""
+    env = os.environ.get
+    p.add_argument("--probe-level", choices=["quick", "deep"],
+                   default=env("CRO_PROBE_LEVEL", "quick"),
+                   help="quick: matrix-pipe and rate gate on attach; deep: "
+                   "additionally verify VRAM and host-link data (adds the "
+                   "sweep time to every attach)")
+    p.add_argument("--probe-vram-mib", type=int,
+                   default=int(env("CRO_PROBE_VRAM_MIB", "0")),
+                   help="deep probe: MiB of VRAM to verify (0 = library default)")
+    p.add_argument("--probe-link-mib", type=int,
+                   default=int(env("CRO_PROBE_LINK_MIB", "0")),
+                   help="deep probe: MiB moved across the host link per "
+                   "direction and path (0 = library default)")
+    p.add_argument("--probe-link-floor-gbps", type=float,
+                   default=float(env("CRO_PROBE_LINK_FLOOR_GBPS", "0")),
+                   help="deep probe: fail when a link rate is below this "
+                   "(0 = off: the link stages gate on data only)")
+
+
+def select_probe_fn(args):
+    """The AmdNodeOps probe hook for the parsed --probe-* options."""
+    from ..nodeops.probe import make_probe_fn
+
+    return make_probe_fn(
+        args.probe_level,
+        vram_bytes=args.probe_vram_mib << 20,
+        link_bytes=args.probe_link_mib << 20,
+        link_floor_gbps=args.probe_link_floor_gbps,
+    )
+
+
 def main(argv=None) -> int:
     from .. import __version__
 
@@ -99,6 +133,7 @@ def main(argv=None) -> int:
                    help="use the in-memory node-path double instead of real "
                    "KFD/sysfs (CI and control-plane demos on GPU-less "
                    "machines; BASELINE config #1 shape)")
+    add_probe_arguments(p)
     p.add_argument("--max-concurrent-reconciles", type=int, default=8)
     p.add_argument("--syncer-period", type=float, default=60.0)
     p.add_argument("--zap-log-level", default="info")
@@ -260,10 +295,12 @@ def main(argv=None) -> int:
         adapter.provider.client = mgr.client
     probe_fn = None
     try:
-        from ..nodeops.probe import load_library, probe_fn_for_nodeops
+        from ..nodeops.probe import load_library
 
         if load_library(required=False) is not None:
-            probe_fn = probe_fn_for_nodeops
+            probe_fn = select_probe_fn(args)
+            if args.probe_level != "quick":
+                log.info("health probe level: %s", args.probe_level)
     except Exception:
         log.warning("gfx950 probe library unavailable; health probe disabled")
     execer = LocalNodeExec()

@@ -361,6 +361,18 @@ class ComposableResourceReconciler(Reconciler):
         with self._phase("health_probe"):
             probe = ops.health_probe(node, resource.status.device_id)
         if probe is not None and not probe.get("ok", True):
+            integrity = probe.get("integrity")
+            if isinstance(integrity, dict) and not integrity.get("ok", True):
+                # deep level: lead with what an operator needs to act on —
+                # which stage, where, which bits — before the raw dict
+                stage = integrity.get("failed_stage") or "unknown"
+                self.metrics.probe_integrity_failures_total.labels(stage=stage).inc()
+                raise FabricError(
+                    "gfx950 health probe failed: integrity stage "
+                    f"{stage} first_bad_byte={integrity.get('first_bad_byte')} "
+                    f"bits_bad=0x{int(integrity.get('bits_bad', 0)):08x} "
+                    f"n_bad={integrity.get('n_bad')}: {probe}"
+                )
             raise FabricError(f"gfx950 health probe failed: {probe}")
 
         resource.status.state = "Online"
@@ -372,6 +384,22 @@ class ComposableResourceReconciler(Reconciler):
                 f"; probe: mfma_exact={probe.get('mfma_f32_exact')} "
                 f"hbm={probe.get('hbm_gbps', 0):.0f} GB/s"
             )
+            integrity = probe.get("integrity")
+            if isinstance(integrity, dict):
+                link = min(
+                    integrity.get("h2d_dma_bytes_verified", 0),
+                    integrity.get("d2h_dma_bytes_verified", 0),
+                )
+                # span, not span x passes
+                vram = integrity.get("vram_bytes_verified", 0) // max(
+                    integrity.get("vram_passes", 1), 1
+                )
+                probe_note += (
+                    f"; integrity: vram {vram / 2**30:.2f} GiB"
+                    f" link {link / 2**30:.2f} GiB verified,"
+                    f" h2d {integrity.get('h2d_dma_gbps', 0):.1f}"
+                    f" d2h {integrity.get('d2h_dma_gbps', 0):.1f} GB/s"
+                )
         self.recorder.normal(
             resource,
             "Online",

@@ -15,20 +15,27 @@ import sys
 HIP_DIR = os.path.dirname(os.path.abspath(__file__))
 AGENT_DIR = os.path.join(os.path.dirname(HIP_DIR), "agent")
 SRC = os.path.join(HIP_DIR, "probe.hip")
+# quick probe + deep (data-integrity) probe, one shared library
+SRCS = [SRC, os.path.join(HIP_DIR, "integrity.hip")]
+HEADERS = [os.path.join(HIP_DIR, "croprobe.h"), os.path.join(HIP_DIR, "cropattern.h")]
 OUT = os.path.join(HIP_DIR, "libcroprobe.so")
 AGENT_SRC = os.path.join(AGENT_DIR, "croagent.cpp")
 AGENT_OUT = os.path.join(AGENT_DIR, "croagent")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
+def _stale(out: str, inputs) -> bool:
+    """True when ``out`` is missing or older than any of its inputs."""
+    if not os.path.exists(out):
+        return True
+    built = os.path.getmtime(out)
+    return any(os.path.getmtime(path) > built for path in inputs)
+
+
 def build(force: bool = False) -> str:
-    if (
-        force
-        or not os.path.exists(OUT)
-        or os.path.getmtime(OUT) < os.path.getmtime(SRC)
-    ):
+    if force or _stale(OUT, SRCS + HEADERS):
         subprocess.run(
-            [HIPCC, "--offload-arch=gfx950", "-O3", "-fPIC", "-shared", SRC, "-o", OUT],
+            [HIPCC, "--offload-arch=gfx950", "-O3", "-fPIC", "-shared", *SRCS, "-o", OUT],
             check=True,
         )
     build_agent(force=force)
@@ -37,11 +44,7 @@ def build(force: bool = False) -> str:
 
 def build_agent(force: bool = False) -> str:
     """croagent: the native node-agent CLI (links libcroprobe)."""
-    if (
-        not force
-        and os.path.exists(AGENT_OUT)
-        and os.path.getmtime(AGENT_OUT) >= os.path.getmtime(AGENT_SRC)
-    ):
+    if not force and not _stale(AGENT_OUT, [AGENT_SRC, HEADERS[0], OUT]):
         return AGENT_OUT
     subprocess.run(
         [

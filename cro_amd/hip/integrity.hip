@@ -1,0 +1,496 @@
+// cro_amd gfx950 deep probe: data integrity of VRAM and of the host link.
+//
+// The quick probe (probe.hip) gates on the matrix pipe and on rates; it
+// never looks at a byte that went through HBM or across the fabric link.
+// This stage does, with an address-dependent pattern (cropattern.h):
+//
+//   vram        — fill every chunk of the span, then verify every chunk
+//                 (all resident, so aliasing between chunks shows), for
+//                 the pattern and for its complement.
+//   h2d_dma     — host writes a pinned buffer → hipMemcpy → device verifies.
+//   d2h_dma     — device fills → hipMemcpy → host verifies.
+//   h2d_kernel  — the verify kernel reads the pinned buffer across the link.
+//   d2h_kernel  — the fill kernel writes the pinned buffer across the link.
+//
+// The same two kernels serve VRAM pointers and device-mapped pinned host
+// pointers.  Gates are on data (any mismatch or HIP error fails); rates are
+// reported, and gated only by the optional link_floor_gbps.
+//
+// Compiled with probe.hip into libcroprobe.so (cro_amd/hip/build.py).
+
+#include <hip/hip_runtime.h>
+#include <chrono>
+#include <cstdio>
+#include <cstring>
+#include <mutex>
+#include <vector>
+
+#include "cropattern.h"
+#include "croprobe.h"
+
+namespace {
+
+struct PatternReport {
+  unsigned long long n_bad;
+  unsigned long long first_bad;  // global word index, all-ones = none
+  unsigned int bits_bad;
+  unsigned int pad;
+};
+
+constexpr int kBlock = 256;
+// 1024 workgroups x 256 lanes x 16 B = 16 MiB (2^20 vectors) per grid pass:
+// 4 workgroups on each of the 256 CUs, grid-stride for the rest.
+constexpr unsigned kMaxGrid = 1024;
+
+// ---------------------------------------------------------------------------
+// kernels
+// ---------------------------------------------------------------------------
+
+__global__ __launch_bounds__(kBlock) void pattern_fill_kernel(
+    uint32_t* __restrict__ dst, uint64_t n_words, uint64_t base_word, uint32_t seed,
+    uint32_t invert) {
+  const uint64_t n4 = n_words >> 2;
+  const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  uint4* __restrict__ d4 = reinterpret_cast<uint4*>(dst);
+  for (uint64_t i = tid; i < n4; i += stride) {
+    const uint64_t w = base_word + (i << 2);
+    uint4 v;
+    v.x = cro_pattern_word(w + 0, seed, invert);
+    v.y = cro_pattern_word(w + 1, seed, invert);
+    v.z = cro_pattern_word(w + 2, seed, invert);
+    v.w = cro_pattern_word(w + 3, seed, invert);
+    d4[i] = v;
+  }
+  const uint64_t tail0 = n4 << 2;  // n_words % 4 trailing words, one lane each
+  if (tid < n_words - tail0)
+    dst[tail0 + tid] = cro_pattern_word(base_word + tail0 + tid, seed, invert);
+}
+
+// Mismatches are counted per wave before anything touches global memory:
+// each compare is balloted across the 64 lanes and the 64-bit mask is
+// popcounted (__popcll — a 32-bit popcount would drop lanes 32-63).  The
+// loop runs on the vector index of lane 0, which every lane of a wave
+// shares, so all 64 lanes reach every ballot and the counters are
+// wave-uniform.  A wave that saw nothing bad issues no atomic at all; one
+// that did issues one add, one min and one or.
+__global__ __launch_bounds__(kBlock) void pattern_verify_kernel(
+    const uint32_t* __restrict__ src, uint64_t n_words, uint64_t base_word,
+    uint32_t seed, uint32_t invert, PatternReport* __restrict__ report) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t n4 = n_words >> 2;
+  const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  const uint4* __restrict__ s4 = reinterpret_cast<const uint4*>(src);
+
+  unsigned long long wave_bad = 0;
+  unsigned long long wave_first = ~0ull;
+  uint32_t bits = 0;  // per lane; reduced only when the wave saw a mismatch
+
+  for (uint64_t i0 = tid - lane; i0 < n4; i0 += stride) {
+    const uint64_t i = i0 + lane;
+    const uint64_t w = base_word + (i << 2);
+    uint4 want;
+    want.x = cro_pattern_word(w + 0, seed, invert);
+    want.y = cro_pattern_word(w + 1, seed, invert);
+    want.z = cro_pattern_word(w + 2, seed, invert);
+    want.w = cro_pattern_word(w + 3, seed, invert);
+    uint4 got = want;  // lanes past the end compare equal
+    if (i < n4) got = s4[i];
+    const uint32_t d[4] = {got.x ^ want.x, got.y ^ want.y, got.z ^ want.z,
+                           got.w ^ want.w};
+    bits |= d[0] | d[1] | d[2] | d[3];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const unsigned long long mask = __ballot(d[j] != 0);
+      if (mask) {
+        wave_bad += (unsigned long long)__popcll(mask);
+        const unsigned long long first =
+            base_word + ((i0 + (uint64_t)(__ffsll(mask) - 1)) << 2) + j;
+        wave_first = first < wave_first ? first : wave_first;
+      }
+    }
+  }
+
+  {  // n_words % 4 trailing words, one lane each (first wave of block 0)
+    const uint64_t tail0 = n4 << 2;
+    uint32_t d = 0;
+    if (tid < n_words - tail0)
+      d = src[tail0 + tid] ^ cro_pattern_word(base_word + tail0 + tid, seed, invert);
+    bits |= d;
+    const unsigned long long mask = __ballot(d != 0);
+    if (mask) {
+      wave_bad += (unsigned long long)__popcll(mask);
+      const unsigned long long first =
+          base_word + tail0 + (tid - lane) + (uint64_t)(__ffsll(mask) - 1);
+      wave_first = first < wave_first ? first : wave_first;
+    }
+  }
+
+  if (wave_bad) {
+    for (int off = 32; off > 0; off >>= 1) bits |= __shfl_xor(bits, off, 64);
+    if (lane == 0) {
+      atomicAdd(&report->n_bad, wave_bad);
+      atomicMin(&report->first_bad, wave_first);
+      atomicOr(&report->bits_bad, bits);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------
+
+double now_ms() {
+  return std::chrono::duration<double, std::milli>(
+             std::chrono::steady_clock::now().time_since_epoch())
+      .count();
+}
+
+unsigned grid_for(uint64_t n_words) {
+  uint64_t blocks = ((n_words >> 2) + kBlock - 1) / kBlock;
+  if (blocks < 1) blocks = 1;  // the tail still needs one workgroup
+  if (blocks > kMaxGrid) blocks = kMaxGrid;
+  return (unsigned)blocks;
+}
+
+void launch_fill(uint32_t* dst, uint64_t n_words, uint64_t base_word, uint32_t seed,
+                 uint32_t invert) {
+  hipLaunchKernelGGL(pattern_fill_kernel, dim3(grid_for(n_words)), dim3(kBlock), 0, 0,
+                     dst, n_words, base_word, seed, invert);
+}
+
+void launch_verify(const uint32_t* src, uint64_t n_words, uint64_t base_word,
+                   uint32_t seed, uint32_t invert, PatternReport* report) {
+  hipLaunchKernelGGL(pattern_verify_kernel, dim3(grid_for(n_words)), dim3(kBlock), 0, 0,
+                     src, n_words, base_word, seed, invert, report);
+}
+
+void host_fill(uint32_t* dst, uint64_t n_words, uint32_t seed, uint32_t invert) {
+  for (uint64_t w = 0; w < n_words; ++w) dst[w] = cro_pattern_word(w, seed, invert);
+}
+
+PatternReport host_verify(const uint32_t* src, uint64_t n_words, uint32_t seed,
+                          uint32_t invert) {
+  PatternReport r = {0, ~0ull, 0, 0};
+  for (uint64_t w = 0; w < n_words; ++w) {
+    const uint32_t d = src[w] ^ cro_pattern_word(w, seed, invert);
+    if (d) {
+      if (r.n_bad == 0) r.first_bad = w;
+      ++r.n_bad;
+      r.bits_bad |= d;
+    }
+  }
+  return r;
+}
+
+const PatternReport kCleanReport = {0, ~0ull, 0, 0};
+
+// Per-device cached context (as ProbeCtx in probe.hip): the pinned link
+// buffer, the events and the report word survive between attaches; VRAM
+// does not.  The mutex serialises concurrent reconcile workers on one
+// device.
+struct IntegCtx {
+  std::mutex mu;
+  int ready = 0;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  PatternReport* d_report = nullptr;
+  uint32_t* pinned = nullptr;      // host address
+  uint32_t* pinned_dev = nullptr;  // the same memory as the device sees it
+  size_t pinned_bytes = 0;
+};
+IntegCtx g_ictx[64];
+
+// VRAM held by one run; released on every way out.
+struct Held {
+  std::vector<uint32_t*> chunks;
+  uint32_t* dlink = nullptr;
+  ~Held() {
+    for (uint32_t* p : chunks) (void)hipFree(p);
+    if (dlink) (void)hipFree(dlink);
+  }
+};
+
+#define ICHECK(expr)                                                         \
+  do {                                                                       \
+    hipError_t _e = (expr);                                                  \
+    if (_e != hipSuccess) {                                                  \
+      snprintf(out->msg, sizeof(out->msg), "%s failed: %s", #expr,           \
+               hipGetErrorString(_e));                                       \
+      out->ok = 0;                                                           \
+      out->rc = -1;                                                          \
+      return -1;                                                             \
+    }                                                                        \
+  } while (0)
+
+int fail_data(CroIntegrityResult* out, const char* stage, const PatternReport& r,
+              unsigned long long stage_base_word) {
+  out->ok = 0;
+  out->rc = -20;
+  out->n_bad = r.n_bad;
+  out->first_bad_byte = (r.first_bad - stage_base_word) * 4ull;
+  out->bits_bad = r.bits_bad;
+  snprintf(out->failed_stage, sizeof(out->failed_stage), "%s", stage);
+  snprintf(out->msg, sizeof(out->msg),
+           "data mismatch in stage %s: %llu bad words, first at byte %llu, bits 0x%08x",
+           stage, out->n_bad, out->first_bad_byte, out->bits_bad);
+  return -20;
+}
+
+double gbps(double bytes, float ms) { return ms > 0.f ? bytes / (ms * 1e6) : 0.0; }
+
+int run_integrity(int device, const CroIntegrityOpts* opts, CroIntegrityResult* out) {
+  const long long kGiB = 1ll << 30;
+  long long vram_bytes = opts && opts->vram_bytes > 0 ? opts->vram_bytes : kGiB;
+  long long link_bytes = opts && opts->link_bytes > 0 ? opts->link_bytes : (256ll << 20);
+  long long chunk_bytes = opts && opts->chunk_bytes > 0 ? opts->chunk_bytes : kGiB;
+  if (chunk_bytes > kGiB) chunk_bytes = kGiB;
+  chunk_bytes &= ~15ll;  // every chunk but the last holds whole 16-byte vectors
+  if (chunk_bytes < 16) chunk_bytes = 16;
+  const uint32_t seed = opts ? opts->seed : 0u;
+  const uint32_t seed_back = seed ^ 0xA5A5A5A5u;  // device→host direction: a stale
+                                                  // host→device image can never pass
+  const double floor_gbps = opts ? opts->link_floor_gbps : 0.0;
+  const uint64_t vram_words = (uint64_t)vram_bytes >> 2;  // whole words only
+  const uint64_t link_words = (uint64_t)link_bytes >> 2;
+  const uint64_t chunk_words = (uint64_t)chunk_bytes >> 2;
+
+  int count = 0;
+  ICHECK(hipGetDeviceCount(&count));
+  if (device < 0 || device >= count || device >= 64) {
+    snprintf(out->msg, sizeof(out->msg), "device %d out of range (%d present)", device,
+             count);
+    out->rc = -1;
+    return -1;
+  }
+  if (vram_words == 0 || link_words == 0) {
+    snprintf(out->msg, sizeof(out->msg), "vram_bytes and link_bytes must be >= 4");
+    out->rc = -1;
+    return -1;
+  }
+  IntegCtx* ctx = &g_ictx[device];
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  ICHECK(hipSetDevice(device));
+  if (!ctx->ready) {
+    ICHECK(hipEventCreate(&ctx->e0));
+    ICHECK(hipEventCreate(&ctx->e1));
+    ICHECK(hipMalloc(&ctx->d_report, sizeof(PatternReport)));
+    ctx->ready = 1;
+  }
+  if (ctx->pinned_bytes < link_words * 4) {
+    if (ctx->pinned) {
+      (void)hipHostFree(ctx->pinned);
+      ctx->pinned = nullptr;
+      ctx->pinned_dev = nullptr;
+      ctx->pinned_bytes = 0;
+    }
+    ICHECK(hipHostMalloc(&ctx->pinned, link_words * 4, hipHostMallocMapped));
+    ICHECK(hipHostGetDevicePointer((void**)&ctx->pinned_dev, ctx->pinned, 0));
+    ctx->pinned_bytes = link_words * 4;
+    // one untimed round trip with the new buffer: the first copy of a
+    // process pays one-time set-up that would understate h2d_dma_gbps
+    const size_t warm = link_words * 4 < (1u << 20) ? link_words * 4 : (1u << 20);
+    void* tmp = nullptr;
+    ICHECK(hipMalloc(&tmp, warm));
+    hipError_t we = hipMemcpy(tmp, ctx->pinned, warm, hipMemcpyHostToDevice);
+    if (we == hipSuccess) we = hipMemcpy(ctx->pinned, tmp, warm, hipMemcpyDeviceToHost);
+    (void)hipFree(tmp);
+    ICHECK(we);
+  }
+  hipEvent_t e0 = ctx->e0, e1 = ctx->e1;
+  PatternReport rep;
+  float ms = 0.f;
+  Held held;
+
+  // -- VRAM ------------------------------------------------------------------
+  double t0 = now_ms();
+  std::vector<uint64_t> chunk_n;
+  for (uint64_t done = 0; done < vram_words;) {
+    const uint64_t n = vram_words - done < chunk_words ? vram_words - done : chunk_words;
+    uint32_t* p = nullptr;
+    ICHECK(hipMalloc(&p, (n * 4 + 15) & ~15ull));
+    held.chunks.push_back(p);
+    chunk_n.push_back(n);
+    done += n;
+  }
+  out->vram_chunks = (int)held.chunks.size();
+  float fill_ms = 0.f, verify_ms = 0.f;
+  for (uint32_t invert = 0; invert < 2; ++invert) {
+    ICHECK(hipEventRecord(e0));
+    uint64_t base = 0;
+    for (size_t c = 0; c < held.chunks.size(); ++c) {
+      launch_fill(held.chunks[c], chunk_n[c], base, seed, invert);
+      base += chunk_n[c];
+    }
+    ICHECK(hipGetLastError());
+    ICHECK(hipEventRecord(e1));
+    ICHECK(hipEventSynchronize(e1));
+    ICHECK(hipEventElapsedTime(&ms, e0, e1));
+    fill_ms += ms;
+
+    ICHECK(hipMemcpy(ctx->d_report, &kCleanReport, sizeof(rep), hipMemcpyHostToDevice));
+    ICHECK(hipEventRecord(e0));
+    base = 0;
+    for (size_t c = 0; c < held.chunks.size(); ++c) {
+      launch_verify(held.chunks[c], chunk_n[c], base, seed, invert, ctx->d_report);
+      base += chunk_n[c];
+    }
+    ICHECK(hipGetLastError());
+    ICHECK(hipEventRecord(e1));
+    ICHECK(hipEventSynchronize(e1));
+    ICHECK(hipEventElapsedTime(&ms, e0, e1));
+    verify_ms += ms;
+    ICHECK(hipMemcpy(&rep, ctx->d_report, sizeof(rep), hipMemcpyDeviceToHost));
+    out->vram_passes = (int)invert + 1;
+    out->vram_bytes_verified += (long long)(vram_words * 4);
+    out->vram_n_bad += rep.n_bad;
+    if (rep.n_bad) return fail_data(out, "vram", rep, 0);
+  }
+  out->vram_fill_gbps = gbps(2.0 * vram_words * 4, fill_ms);
+  out->vram_verify_gbps = gbps(2.0 * vram_words * 4, verify_ms);
+  for (uint32_t* p : held.chunks) ICHECK(hipFree(p));
+  held.chunks.clear();
+  out->t_vram_ms = now_ms() - t0;
+
+  // -- link, copy engines ------------------------------------------------------
+  t0 = now_ms();
+  const double lbytes = (double)(link_words * 4);
+  ICHECK(hipMalloc(&held.dlink, (link_words * 4 + 15) & ~15ull));
+  host_fill(ctx->pinned, link_words, seed, 0);
+  ICHECK(hipEventRecord(e0));
+  ICHECK(hipMemcpy(held.dlink, ctx->pinned, link_words * 4, hipMemcpyHostToDevice));
+  ICHECK(hipEventRecord(e1));
+  ICHECK(hipEventSynchronize(e1));
+  ICHECK(hipEventElapsedTime(&ms, e0, e1));
+  out->h2d_dma_gbps = gbps(lbytes, ms);
+  ICHECK(hipMemcpy(ctx->d_report, &kCleanReport, sizeof(rep), hipMemcpyHostToDevice));
+  launch_verify(held.dlink, link_words, 0, seed, 0, ctx->d_report);
+  ICHECK(hipGetLastError());
+  ICHECK(hipMemcpy(&rep, ctx->d_report, sizeof(rep), hipMemcpyDeviceToHost));
+  out->link_passes = 1;
+  out->h2d_dma_bytes_verified = (long long)(link_words * 4);
+  out->h2d_dma_n_bad = rep.n_bad;
+  if (rep.n_bad) return fail_data(out, "h2d_dma", rep, 0);
+
+  launch_fill(held.dlink, link_words, 0, seed_back, 0);
+  ICHECK(hipGetLastError());
+  ICHECK(hipDeviceSynchronize());
+  ICHECK(hipEventRecord(e0));
+  ICHECK(hipMemcpy(ctx->pinned, held.dlink, link_words * 4, hipMemcpyDeviceToHost));
+  ICHECK(hipEventRecord(e1));
+  ICHECK(hipEventSynchronize(e1));
+  ICHECK(hipEventElapsedTime(&ms, e0, e1));
+  out->d2h_dma_gbps = gbps(lbytes, ms);
+  rep = host_verify(ctx->pinned, link_words, seed_back, 0);
+  out->d2h_dma_bytes_verified = (long long)(link_words * 4);
+  out->d2h_dma_n_bad = rep.n_bad;
+  if (rep.n_bad) return fail_data(out, "d2h_dma", rep, 0);
+  ICHECK(hipFree(held.dlink));
+  held.dlink = nullptr;
+  out->t_link_dma_ms = now_ms() - t0;
+
+  // -- link, shader loads and stores (complement pattern) ----------------------
+  t0 = now_ms();
+  host_fill(ctx->pinned, link_words, seed, 1);
+  ICHECK(hipMemcpy(ctx->d_report, &kCleanReport, sizeof(rep), hipMemcpyHostToDevice));
+  ICHECK(hipEventRecord(e0));
+  launch_verify(ctx->pinned_dev, link_words, 0, seed, 1, ctx->d_report);
+  ICHECK(hipGetLastError());
+  ICHECK(hipEventRecord(e1));
+  ICHECK(hipEventSynchronize(e1));
+  ICHECK(hipEventElapsedTime(&ms, e0, e1));
+  out->h2d_kernel_gbps = gbps(lbytes, ms);
+  ICHECK(hipMemcpy(&rep, ctx->d_report, sizeof(rep), hipMemcpyDeviceToHost));
+  out->h2d_kernel_bytes_verified = (long long)(link_words * 4);
+  out->h2d_kernel_n_bad = rep.n_bad;
+  if (rep.n_bad) return fail_data(out, "h2d_kernel", rep, 0);
+
+  ICHECK(hipEventRecord(e0));
+  launch_fill(ctx->pinned_dev, link_words, 0, seed_back, 1);
+  ICHECK(hipGetLastError());
+  ICHECK(hipEventRecord(e1));
+  ICHECK(hipEventSynchronize(e1));
+  ICHECK(hipEventElapsedTime(&ms, e0, e1));
+  out->d2h_kernel_gbps = gbps(lbytes, ms);
+  ICHECK(hipDeviceSynchronize());
+  rep = host_verify(ctx->pinned, link_words, seed_back, 1);
+  out->d2h_kernel_bytes_verified = (long long)(link_words * 4);
+  out->d2h_kernel_n_bad = rep.n_bad;
+  if (rep.n_bad) return fail_data(out, "d2h_kernel", rep, 0);
+  out->t_link_kernel_ms = now_ms() - t0;
+
+  if (floor_gbps > 0.0) {
+    const struct { const char* stage; double rate; } rates[] = {
+        {"h2d_dma", out->h2d_dma_gbps},       {"d2h_dma", out->d2h_dma_gbps},
+        {"h2d_kernel", out->h2d_kernel_gbps}, {"d2h_kernel", out->d2h_kernel_gbps}};
+    for (const auto& r : rates) {
+      if (r.rate < floor_gbps) {
+        out->rc = -21;
+        snprintf(out->failed_stage, sizeof(out->failed_stage), "%s", r.stage);
+        snprintf(out->msg, sizeof(out->msg),
+                 "link rate %.1f GB/s in stage %s below floor %.1f GB/s", r.rate, r.stage,
+                 floor_gbps);
+        return -21;
+      }
+    }
+  }
+  out->ok = 1;
+  snprintf(out->msg, sizeof(out->msg), "ok");
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int cro_probe_integrity(int device, const struct CroIntegrityOpts* opts,
+                                   struct CroIntegrityResult* out) {
+  memset(out, 0, sizeof(*out));
+  out->first_bad_byte = ~0ull;
+  const double t0 = now_ms();
+  int rc = run_integrity(device, opts, out);
+  out->t_total_ms = now_ms() - t0;
+  return rc;
+}
+
+extern "C" int cro_probe_pattern_fill(int device, unsigned int seed, int invert,
+                                      unsigned long long base_word,
+                                      unsigned long long n_words, unsigned int* host_out) {
+  if (n_words == 0 || host_out == nullptr) return -10;
+  if (hipSetDevice(device) != hipSuccess) return -1;
+  uint32_t* d = nullptr;
+  if (hipMalloc(&d, (n_words * 4 + 15) & ~15ull) != hipSuccess) return -1;
+  launch_fill(d, n_words, base_word, seed, invert ? 1u : 0u);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpy(host_out, d, n_words * 4, hipMemcpyDeviceToHost);
+  (void)hipFree(d);
+  return e == hipSuccess ? 0 : -1;
+}
+
+extern "C" int cro_probe_pattern_verify(int device, unsigned int seed, int invert,
+                                        unsigned long long base_word,
+                                        unsigned long long n_words,
+                                        const unsigned int* host_in,
+                                        unsigned long long* n_bad,
+                                        unsigned long long* first_bad,
+                                        unsigned int* bits_bad) {
+  if (n_words == 0 || host_in == nullptr) return -10;
+  if (hipSetDevice(device) != hipSuccess) return -1;
+  uint32_t* d = nullptr;
+  PatternReport* d_rep = nullptr;
+  PatternReport rep = kCleanReport;
+  hipError_t e = hipMalloc(&d, (n_words * 4 + 15) & ~15ull);
+  if (e == hipSuccess) e = hipMalloc(&d_rep, sizeof(rep));
+  if (e == hipSuccess) e = hipMemcpy(d, host_in, n_words * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_rep, &rep, sizeof(rep), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    launch_verify(d, n_words, base_word, seed, invert ? 1u : 0u, d_rep);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(&rep, d_rep, sizeof(rep), hipMemcpyDeviceToHost);
+  if (d) (void)hipFree(d);
+  if (d_rep) (void)hipFree(d_rep);
+  if (e != hipSuccess) return -1;
+  if (n_bad) *n_bad = rep.n_bad;
+  if (first_bad) *first_bad = rep.first_bad;
+  if (bits_bad) *bits_bad = rep.bits_bad;
+  return 0;
+}

@@ -67,6 +67,13 @@ class Metrics:
         self.devices_online = Gauge(
             "cro_devices_online", "ComposableResources currently Online"
         )
+        self.probe_integrity_failures_total = Counter(
+            "cro_probe_integrity_failures_total",
+            "Attaches refused by the deep probe's data-integrity stage, by "
+            "the stage that failed (vram, h2d_dma, d2h_dma, h2d_kernel, "
+            "d2h_kernel)",
+            ["stage"],
+        )
 
     # test helper: drop collectors so a fresh interpreter state can be faked
     @classmethod
@@ -79,6 +86,7 @@ class Metrics:
                 cls._singleton.reconcile_total,
                 cls._singleton.fabric_request_seconds,
                 cls._singleton.devices_online,
+                cls._singleton.probe_integrity_failures_total,
             ):
                 try:
                     REGISTRY.unregister(collector)
