@@ -6,7 +6,8 @@ FROM rocm/dev-ubuntu-22.04:7.2 AS build
 WORKDIR /src
 COPY cro_amd/ cro_amd/
 RUN /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -shared \
-      cro_amd/hip/probe.hip cro_amd/hip/integrity.hip -o cro_amd/hip/libcroprobe.so && \
+      cro_amd/hip/probe.hip cro_amd/hip/integrity.hip cro_amd/hip/coverage.hip \
+      -o cro_amd/hip/libcroprobe.so && \
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O2 \
       cro_amd/agent/croagent.cpp -Lcro_amd/hip -lcroprobe \
       -Wl,-rpath,'$ORIGIN/../hip' -o cro_amd/agent/croagent

@@ -13,6 +13,8 @@
 //   croagent probe  [--device N | --bdf B]   gfx950 MFMA/HBM health probe
 //       [--deep [--vram-mib N] [--link-mib N] [--link-floor-gbps X]]
 //                                            + VRAM / host-link data integrity
+//       [--compute [--compute-min-cu-fraction X]]
+//                                            + exact checks on every CU and SIMD
 //   croagent drain  --bdf 0000:5a:00.0       sysfs PCI remove
 //   croagent rescan                          sysfs PCI rescan
 //
@@ -297,24 +299,64 @@ void print_integrity(const CroIntegrityResult& r) {
          r.t_vram_ms, r.t_link_dma_ms, r.t_link_kernel_ms, r.t_total_ms, r.msg);
 }
 
-// --deep: the quick probe first; a device that failed it is not stressed
-// further.  Top-level "ok" and "msg" then cover both stages.
-int cmd_probe_deep(int device, const CroIntegrityOpts& opts) {
+void print_compute(const CroComputeResult& r) {
+  const CroCoverageAgg& a = r.agg;
+  printf("\"compute\":{\"ok\":%s,\"rc\":%d,\"cus_expected\":%d,\"rounds\":%d,"
+         "\"waves_run\":%llu,\"waves_bad\":%llu,\"bad_f32\":%llu,\"bad_i8\":%llu,"
+         "\"bad_bf16\":%llu,\"bad_lds\":%llu,\"first_bad_index\":%lld,",
+         r.ok ? "true" : "false", r.rc, r.cus_expected, r.rounds, a.waves_run, a.waves_bad,
+         a.bad_f32, a.bad_i8, a.bad_bf16, a.bad_lds, a.first_bad_index);
+  printf("\"cus_seen\":%d,\"xcds_seen\":%d,\"simds_seen\":%d,\"cus_bad\":%d,\"xcd\":%d,"
+         "\"se\":%d,\"sh\":%d,\"cu\":%d,\"simd\":%d,\"first_fail_mask\":%u,\"n_bad\":%u,"
+         "\"first_bad\":%u,\"bits_bad\":%u,\"n_bad_cu_keys\":%d,\"bad_cu_keys\":[",
+         a.cus_seen, a.xcds_seen, a.simds_seen, a.cus_bad, a.xcd, a.se, a.sh, a.cu, a.simd,
+         a.first_fail_mask, a.n_bad, a.first_bad, a.bits_bad, a.n_bad_cu_keys);
+  for (int i = 0; i < a.n_bad_cu_keys; ++i) printf("%s%u", i ? "," : "", a.bad_cu_keys[i]);
+  printf("],\"first_bad_round\":%d,\"first_bad_record\":%d,\"grid_blocks\":%d,"
+         "\"lds_bytes\":%d,\"iters\":%d,\"gpu_ms\":%.3f,\"t_total_ms\":%.3f,"
+         "\"failed_test\":\"%s\",\"msg\":\"%s\"}",
+         r.first_bad_round, r.first_bad_record, r.grid_blocks, r.lds_bytes, r.iters, r.gpu_ms,
+         r.t_total_ms, r.failed_test, r.msg);
+}
+
+// --compute and/or --deep: the quick probe first, then the compute-coverage
+// stage, then the data-integrity stage; a device that failed a stage is not
+// stressed further.  Top-level "ok" and "msg" then cover all stages run.
+int cmd_probe_staged(int device, bool compute, const CroComputeOpts& copts, bool deep,
+                     const CroIntegrityOpts& opts) {
   CroProbeResult result;
   int rc = cro_probe_run(device, &result);
+  CroComputeResult comp;
   CroIntegrityResult integ;
-  bool ran = false;
-  if (result.ok) {
+  bool ran_comp = false, ran = false;
+  bool ok = result.ok;
+  const char* msg = result.msg;
+  if (ok && compute) {
+    cro_probe_compute(device, &copts, &comp);
+    ran_comp = true;
+    if (!comp.ok) {
+      ok = false;
+      msg = comp.msg;
+    }
+  }
+  if (ok && deep) {
     cro_probe_integrity(device, &opts, &integ);
     ran = true;
+    if (!integ.ok) {
+      ok = false;
+      msg = integ.msg;
+    }
   }
-  bool ok = result.ok && ran && integ.ok;
   printf("{\"ok\":%s,\"rc\":%d,\"mfma_f32_exact\":%s,\"hbm_gbps\":%.1f,"
          "\"bf16_tflops\":%.1f,\"vram_total\":%lld,\"vram_free\":%lld,"
          "\"gcn_arch\":\"%s\",\"msg\":\"%s\"",
          ok ? "true" : "false", rc, result.mfma_f32_exact ? "true" : "false",
          result.hbm_gbps, result.bf16_tflops, result.vram_total, result.vram_free,
-         result.gcn_arch, (ran && !integ.ok) ? integ.msg : result.msg);
+         result.gcn_arch, msg);
+  if (ran_comp) {
+    printf(",");
+    print_compute(comp);
+  }
   if (ran) {
     printf(",");
     print_integrity(integ);
@@ -346,9 +388,11 @@ int main(int argc, char** argv) {
   std::string bdf;
   long long gpu_id = -1;
   int device = 0;
-  bool deep = false;
+  bool deep = false, compute = false;
   CroIntegrityOpts integ_opts;
   memset(&integ_opts, 0, sizeof(integ_opts));
+  CroComputeOpts compute_opts;  // no self-test options here: those are for tests
+  memset(&compute_opts, 0, sizeof(compute_opts));
   for (int i = 2; i < argc; ++i) {
     std::string arg = argv[i];
     if (arg == "--sysroot" && i + 1 < argc) g_sysroot = argv[++i];
@@ -356,6 +400,8 @@ int main(int argc, char** argv) {
     else if (arg == "--gpu-id" && i + 1 < argc) gpu_id = atoll(argv[++i]);
     else if (arg == "--device" && i + 1 < argc) device = atoi(argv[++i]);
     else if (arg == "--deep") deep = true;
+    else if (arg == "--compute") compute = true;
+    else if (arg == "--compute-min-cu-fraction" && i + 1 < argc) compute_opts.min_cu_fraction = atof(argv[++i]);
     else if (arg == "--vram-mib" && i + 1 < argc) integ_opts.vram_bytes = atoll(argv[++i]) << 20;
     else if (arg == "--link-mib" && i + 1 < argc) integ_opts.link_bytes = atoll(argv[++i]) << 20;
     else if (arg == "--link-floor-gbps" && i + 1 < argc) integ_opts.link_floor_gbps = atof(argv[++i]);
@@ -373,7 +419,8 @@ int main(int argc, char** argv) {
         return 1;
       }
     }
-    return deep ? cmd_probe_deep(device, integ_opts) : cmd_probe(device);
+    if (deep || compute) return cmd_probe_staged(device, compute, compute_opts, deep, integ_opts);
+    return cmd_probe(device);
   }
   if (cmd == "drain") return cmd_drain(bdf);
   if (cmd == "rescan") return cmd_rescan();

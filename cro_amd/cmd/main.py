@@ -47,8 +47,8 @@ def parse_port(addr: str, default: int) -> int:
 
 
 def add_probe_arguments(p: argparse.ArgumentParser) -> None:
-    """Health-probe level and the deep level's sizes (env defaults are read
-    when the parser is built)."""
+    """Health-probe level, the deep level's sizes and the compute-coverage
+    switch (env defaults are read when the parser is built)."""
     env = os.environ.get
     p.add_argument("--probe-level", choices=["quick", "deep"],
                    default=env("CRO_PROBE_LEVEL", "quick"),
@@ -66,6 +66,16 @@ def add_probe_arguments(p: argparse.ArgumentParser) -> None:
                    default=float(env("CRO_PROBE_LINK_FLOOR_GBPS", "0")),
                    help="deep probe: fail when a link rate is below this "
                    "(0 = off: the link stages gate on data only)")
+    p.add_argument("--probe-compute", choices=["off", "on"],
+                   default=env("CRO_PROBE_COMPUTE", "off"),
+                   help="on: additionally run exact f32/i8/bf16 matrix checks "
+                   "and an LDS march on every CU and SIMD, at either level; a "
+                   "failure names the XCD, CU and SIMD")
+    p.add_argument("--probe-compute-min-cu-fraction", type=float,
+                   default=float(env("CRO_PROBE_COMPUTE_MIN_CU_FRACTION", "0")),
+                   help="compute probe: fail when fewer than this fraction of "
+                   "the device's CUs were reached (0 = off: coverage is "
+                   "reported, only data gates)")
 
 
 def select_probe_fn(args):
@@ -77,6 +87,8 @@ def select_probe_fn(args):
         vram_bytes=args.probe_vram_mib << 20,
         link_bytes=args.probe_link_mib << 20,
         link_floor_gbps=args.probe_link_floor_gbps,
+        compute=args.probe_compute == "on",
+        compute_min_cu_fraction=args.probe_compute_min_cu_fraction,
     )
 
 
@@ -301,6 +313,8 @@ def main(argv=None) -> int:
             probe_fn = select_probe_fn(args)
             if args.probe_level != "quick":
                 log.info("health probe level: %s", args.probe_level)
+            if args.probe_compute == "on":
+                log.info("health probe compute-coverage stage: on")
     except Exception:
         log.warning("gfx950 probe library unavailable; health probe disabled")
     execer = LocalNodeExec()

@@ -361,6 +361,21 @@ class ComposableResourceReconciler(Reconciler):
         with self._phase("health_probe"):
             probe = ops.health_probe(node, resource.status.device_id)
         if probe is not None and not probe.get("ok", True):
+            compute = probe.get("compute")
+            if isinstance(compute, dict) and not compute.get("ok", True):
+                # compute stage: lead with the check and where on the chip it
+                # failed — what an RMA or a CU mask needs — before the raw dict
+                test = compute.get("failed_test") or (
+                    "coverage" if compute.get("rc") == -31 else "unknown"
+                )
+                self.metrics.probe_compute_failures_total.labels(test=test).inc()
+                raise FabricError(
+                    "gfx950 health probe failed: compute stage "
+                    f"{test} xcd={compute.get('xcd')} se={compute.get('se')} "
+                    f"cu={compute.get('cu')} simd={compute.get('simd')} "
+                    f"bits_bad=0x{int(compute.get('bits_bad', 0)):08x} "
+                    f"cus_bad={compute.get('cus_bad')}: {probe}"
+                )
             integrity = probe.get("integrity")
             if isinstance(integrity, dict) and not integrity.get("ok", True):
                 # deep level: lead with what an operator needs to act on —
@@ -384,6 +399,13 @@ class ComposableResourceReconciler(Reconciler):
                 f"; probe: mfma_exact={probe.get('mfma_f32_exact')} "
                 f"hbm={probe.get('hbm_gbps', 0):.0f} GB/s"
             )
+            compute = probe.get("compute")
+            if isinstance(compute, dict):
+                probe_note += (
+                    f"; compute: {compute.get('cus_seen', 0)}/{compute.get('cus_expected', 0)}"
+                    f" CUs, {compute.get('simds_seen', 0)} SIMDs,"
+                    f" {compute.get('gpu_ms', 0):.1f} ms"
+                )
             integrity = probe.get("integrity")
             if isinstance(integrity, dict):
                 link = min(

@@ -18,6 +18,12 @@ SRC = os.path.join(HIP_DIR, "probe.hip")
 # quick probe + deep (data-integrity) probe, one shared library
 SRCS = [SRC, os.path.join(HIP_DIR, "integrity.hip")]
 HEADERS = [os.path.join(HIP_DIR, "croprobe.h"), os.path.join(HIP_DIR, "cropattern.h")]
+# compute-coverage stage: one more source and header of the same library
+# (listed apart: tests/test_probe_integrity.py pins what SRCS and HEADERS hold)
+COVERAGE_SRC = os.path.join(HIP_DIR, "coverage.hip")
+COVERAGE_HEADER = os.path.join(HIP_DIR, "crocoverage.h")
+ALL_SRCS = SRCS + [COVERAGE_SRC]
+ALL_HEADERS = HEADERS + [COVERAGE_HEADER]
 OUT = os.path.join(HIP_DIR, "libcroprobe.so")
 AGENT_SRC = os.path.join(AGENT_DIR, "croagent.cpp")
 AGENT_OUT = os.path.join(AGENT_DIR, "croagent")
@@ -33,9 +39,9 @@ def _stale(out: str, inputs) -> bool:
 
 
 def build(force: bool = False) -> str:
-    if force or _stale(OUT, SRCS + HEADERS):
+    if force or _stale(OUT, ALL_SRCS + ALL_HEADERS):
         subprocess.run(
-            [HIPCC, "--offload-arch=gfx950", "-O3", "-fPIC", "-shared", *SRCS, "-o", OUT],
+            [HIPCC, "--offload-arch=gfx950", "-O3", "-fPIC", "-shared", *ALL_SRCS, "-o", OUT],
             check=True,
         )
     build_agent(force=force)
@@ -44,7 +50,7 @@ def build(force: bool = False) -> str:
 
 def build_agent(force: bool = False) -> str:
     """croagent: the native node-agent CLI (links libcroprobe)."""
-    if not force and not _stale(AGENT_OUT, [AGENT_SRC, HEADERS[0], OUT]):
+    if not force and not _stale(AGENT_OUT, [AGENT_SRC, HEADERS[0], COVERAGE_HEADER, OUT]):
         return AGENT_OUT
     subprocess.run(
         [

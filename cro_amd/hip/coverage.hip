@@ -1,0 +1,625 @@
+// cro_amd gfx950 compute-coverage probe: exact checks on every CU and SIMD,
+// with fault location.
+//
+// The quick probe (probe.hip) compares one wave's f32 MFMA on one CU; its
+// bf16 rate kernel runs everywhere and compares nothing; no probe kernel
+// touches LDS.  This stage launches one 256-thread workgroup per CU — the
+// default dynamic-LDS request is a CU's whole 160 KiB, which is what places
+// one workgroup per CU and, with four waves, one wave per SIMD — and each
+// wave, `iters` times:
+//
+//   mfma_f32   v_mfma_f32_16x16x4_f32, K = 64, against the host fmaf chain
+//   mfma_i8    v_mfma_i32_16x16x64_i8, K = 256, against an integer product
+//   mfma_bf16  v_mfma_f32_32x32x16_bf16, K = 64, small integers, so the f32
+//              result is exact in any summation order
+//   lds        the workgroup writes the cropattern.h word of every LDS word
+//              with 16-byte stores, verifies with 16-byte loads, then the
+//              complement
+//
+// Every comparison is exact and made on the device, each lane on its own
+// registers; mismatches are counted per wave with a 64-lane ballot and a
+// 64-bit popcount (as integrity.hip).  Each wave reads where it ran
+// (XCC_ID, HW_ID) and lane 0 writes one CroCoverageRecord.  Workgroups are
+// independent: no inter-workgroup communication, no spin, no grid barrier.
+// The host aggregates the records (crocoverage.h) and launches the same grid
+// again, a bounded number of times, while some CU or SIMD is still unseen.
+// The location is for the report only; HIP promises nothing about placement,
+// so coverage gates only when the caller sets min_cu_fraction.
+//
+// Compiled with probe.hip and integrity.hip into libcroprobe.so.
+
+#include <hip/hip_runtime.h>
+#include <chrono>
+#include <cstdio>
+#include <cstring>
+#include <mutex>
+#include <vector>
+
+#include "cropattern.h"
+#include "croprobe.h"
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
+
+constexpr int kBlock = 256;
+constexpr int kWaves = kBlock / 64;
+// ≈0.035 ms per repeat on an MI355X: 16 keeps the stage at the cost of one of
+// the quick probe's rate sections (profiles/compute_probe_mi355x.md)
+constexpr int kDefaultIters = 16;
+constexpr int kDefaultRounds = 4;
+constexpr int kMaxRounds = 64;
+constexpr int kMaxGrid = 1 << 16;
+constexpr int kMaxIters = 1 << 16;
+constexpr int kMaxTileK = 4096;
+
+// ---------------------------------------------------------------------------
+// one wave's matrix products (shared by the coverage kernel and the raw tile
+// entry).  Operand lane maps, lane l of 64:
+//   f32 16x16x4   A[l&15][k = l>>4],             B[k = l>>4][l&15]
+//   i8  16x16x64  A[l&15][k = 16(l>>4) + j],     B[k = 16(l>>4) + j][l&15]
+//                 j = 0..15, byte j&3 of register j>>2 (derived from the
+//                 bf16 16x16x32 map; proved bit-exactly on the GPU by the
+//                 lane-map tests through cro_probe_mfma_tile)
+//   bf16 32x32x16 A[l&31][k = 8(l>>5) + j],      B[k = 8(l>>5) + j][l&31]
+// Result maps (dtype-independent): 16x16 register r is row 4(l>>4) + r,
+// column l&15; 32x32 register r is row (r&3) + 8(r>>2) + 4(l>>5), column l&31.
+// ---------------------------------------------------------------------------
+
+__device__ inline f32x4 wave_mfma_f32(const float* __restrict__ A,
+                                      const float* __restrict__ B, int K, uint32_t lane) {
+  const uint32_t rc = lane & 15, kh = lane >> 4;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  for (int k0 = 0; k0 < K; k0 += 4) {
+    const float a = A[rc * K + (k0 + kh)];
+    const float b = B[(k0 + kh) * 16 + rc];
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);
+  }
+  return acc;
+}
+
+// A rows are 16-byte aligned: K is a multiple of 64 and the base comes from
+// hipMalloc.
+__device__ inline i32x4 wave_mfma_i8(const int8_t* __restrict__ A,
+                                     const int8_t* __restrict__ B, int K, uint32_t lane) {
+  const uint32_t rc = lane & 15, kh = lane >> 4;
+  i32x4 acc = {0, 0, 0, 0};
+  for (int k0 = 0; k0 < K; k0 += 64) {
+    const int kb = k0 + 16 * (int)kh;
+    const i32x4 a = *reinterpret_cast<const i32x4*>(A + rc * K + kb);
+    i32x4 b;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      uint32_t w = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        w |= (uint32_t)(uint8_t)B[(kb + 4 * q + j) * 16 + rc] << (8 * j);
+      b[q] = (int)w;
+    }
+    acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, acc, 0, 0, 0);
+  }
+  return acc;
+}
+
+__device__ inline f32x16 wave_mfma_bf16(const uint16_t* __restrict__ A,
+                                        const uint16_t* __restrict__ B, int K,
+                                        uint32_t lane) {
+  const uint32_t rc = lane & 31, h = lane >> 5;
+  f32x16 acc = {};
+  for (int k0 = 0; k0 < K; k0 += 16) {
+    const int kb = k0 + 8 * (int)h;
+    const u16x8 au = *reinterpret_cast<const u16x8*>(A + rc * K + kb);
+    u16x8 bu;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) bu[j] = B[(kb + j) * 32 + rc];
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, au),
+                                                  __builtin_bit_cast(bf16x8, bu), acc, 0, 0,
+                                                  0);
+  }
+  return acc;
+}
+
+__global__ __launch_bounds__(64) void mfma_tile_kernel(int kind, const void* A, const void* B,
+                                                       void* D, int K) {
+  const uint32_t lane = threadIdx.x;  // exactly one wave of 64
+  if (kind == 1) {
+    const i32x4 acc = wave_mfma_i8((const int8_t*)A, (const int8_t*)B, K, lane);
+    for (int r = 0; r < 4; ++r) ((int*)D)[((lane >> 4) * 4 + r) * 16 + (lane & 15)] = acc[r];
+  } else {
+    const f32x16 acc = wave_mfma_bf16((const uint16_t*)A, (const uint16_t*)B, K, lane);
+    for (int r = 0; r < 16; ++r)
+      ((float*)D)[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * 32 + (lane & 31)] = acc[r];
+  }
+}
+
+// ---------------------------------------------------------------------------
+// coverage kernel
+// ---------------------------------------------------------------------------
+
+struct CovParams {
+  const float* A32;
+  const float* B32;
+  const float* E32;  // expected 16x16
+  const int8_t* A8;
+  const int8_t* B8;
+  const int* E8;  // expected 16x16
+  const uint16_t* A16;
+  const uint16_t* B16;
+  const float* E16;  // expected 32x32
+  CroCoverageRecord* records;  // this round's grid_blocks * 4 records
+  uint32_t lds_words;
+  uint32_t iters;
+  uint32_t seed;
+  uint32_t inj_mode;  // self-test, see croprobe.h
+  uint32_t inj_test;
+  uint32_t inj_elem;
+  uint32_t inj_flip;  // 1 << selftest_bit
+  uint32_t inj_key;
+};
+
+// What one wave found in one test.  n_bad is wave-uniform (ballot counts);
+// first and bits are per lane until reduce().
+struct Tally {
+  uint32_t n_bad = 0;
+  uint32_t first = ~0u;
+  uint32_t bits = 0;
+
+  __device__ void add(uint32_t diff, uint32_t elem) {
+    bits |= diff;
+    const unsigned long long mask = __ballot(diff != 0);
+    if (mask) {
+      n_bad += (uint32_t)__popcll(mask);
+      if (diff) first = elem < first ? elem : first;
+    }
+  }
+  // every lane of the wave calls it (n_bad is uniform, so the branch is)
+  __device__ void reduce() {
+    if (!n_bad) return;
+    for (int off = 32; off > 0; off >>= 1) {
+      bits |= __shfl_xor(bits, off, 64);
+      const uint32_t other = __shfl_xor(first, off, 64);
+      first = other < first ? other : first;
+    }
+  }
+};
+
+__device__ inline uint32_t f32_bits(float x) { return __builtin_bit_cast(uint32_t, x); }
+
+__device__ inline uint4 lds_want(uint64_t base_word, uint32_t v, uint32_t seed,
+                                 uint32_t invert) {
+  const uint64_t w = base_word + ((uint64_t)v << 2);
+  uint4 want;
+  want.x = cro_pattern_word(w + 0, seed, invert);
+  want.y = cro_pattern_word(w + 1, seed, invert);
+  want.z = cro_pattern_word(w + 2, seed, invert);
+  want.w = cro_pattern_word(w + 3, seed, invert);
+  return want;
+}
+
+__global__ __launch_bounds__(kBlock) void coverage_kernel(CovParams p) {
+  // all LDS is dynamic, so its base stays 16-byte aligned for the b128 accesses
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  uint4* lds4 = reinterpret_cast<uint4*>(smem);
+
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  uint32_t xcc_id, hw_id;  // for the report only
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc_id));
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw_id));
+  // self-test mode 2 flips computed values on the waves of one CU; mode 1 is
+  // done on the host except for LDS, whose expected words are computed here
+  const bool inj_computed = p.inj_mode == 2 && cro_cov_cu_key(xcc_id, hw_id) == p.inj_key;
+  const bool inj_lds =
+      p.inj_test == CRO_COV_TEST_LDS && (p.inj_mode == 1 || inj_computed);
+  const uint32_t inj_vec = p.inj_elem >> 2, inj_word = p.inj_elem & 3;
+
+  // the elements this lane holds
+  uint32_t elem16[4], elem32[16];
+  float want_f32[4], want_bf16[16];
+  int want_i8[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    elem16[r] = ((lane >> 4) * 4 + r) * 16 + (lane & 15);
+    want_f32[r] = p.E32[elem16[r]];
+    want_i8[r] = p.E8[elem16[r]];
+  }
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    elem32[r] = ((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * 32 + (lane & 31);
+    want_bf16[r] = p.E16[elem32[r]];
+  }
+
+  Tally t_f32, t_i8, t_bf16, t_lds;
+  const uint32_t n4 = p.lds_words >> 2;
+  const uint64_t lds_base = (uint64_t)blockIdx.x * p.lds_words;
+
+  for (uint32_t it = 0; it < p.iters; ++it) {
+    // an offset of zero the compiler cannot see through: the products are
+    // recomputed, operands reloaded, in every iteration
+    uint32_t z = 0;
+    asm volatile("" : "+v"(z));
+
+    {
+      const f32x4 acc = wave_mfma_f32(p.A32 + z, p.B32 + z, CRO_COV_F32_K, lane);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        uint32_t got = f32_bits(acc[r]);
+        if (inj_computed && p.inj_test == CRO_COV_TEST_F32 && elem16[r] == p.inj_elem)
+          got ^= p.inj_flip;
+        t_f32.add(got ^ f32_bits(want_f32[r]), elem16[r]);
+      }
+    }
+    {
+      const i32x4 acc = wave_mfma_i8(p.A8 + z, p.B8 + z, CRO_COV_I8_K, lane);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        uint32_t got = (uint32_t)acc[r];
+        if (inj_computed && p.inj_test == CRO_COV_TEST_I8 && elem16[r] == p.inj_elem)
+          got ^= p.inj_flip;
+        t_i8.add(got ^ (uint32_t)want_i8[r], elem16[r]);
+      }
+    }
+    {
+      const f32x16 acc = wave_mfma_bf16(p.A16 + z, p.B16 + z, CRO_COV_BF16_K, lane);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        uint32_t got = f32_bits(acc[r]);
+        if (inj_computed && p.inj_test == CRO_COV_TEST_BF16 && elem32[r] == p.inj_elem)
+          got ^= p.inj_flip;
+        t_bf16.add(got ^ f32_bits(want_bf16[r]), elem32[r]);
+      }
+    }
+
+    // LDS march.  Thread t owns vectors t, t + 256, ...; the verify loop
+    // runs on lane 0's vector index, which a wave shares, so all 64 lanes
+    // reach every ballot.
+    for (uint32_t invert = 0; invert < 2; ++invert) {
+      for (uint32_t v = tid; v < n4; v += kBlock) lds4[v] = lds_want(lds_base, v, p.seed, invert);
+      __syncthreads();
+      for (uint32_t v0 = tid - lane; v0 < n4; v0 += kBlock) {
+        const uint32_t v = v0 + lane;
+        const uint4 want = lds_want(lds_base, v, p.seed, invert);
+        uint4 got = want;  // lanes past the end compare equal
+        if (v < n4) got = lds4[v];
+        const uint32_t d[4] = {got.x ^ want.x, got.y ^ want.y, got.z ^ want.z,
+                               got.w ^ want.w};
+        // the same lane and trip in each of the four waves (bits 7:6 of v)
+        const bool hit = inj_lds && v < n4 && ((v ^ inj_vec) & ~0xC0u) == 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          t_lds.add(hit && inj_word == (uint32_t)j ? d[j] ^ p.inj_flip : d[j], (v << 2) + j);
+      }
+      __syncthreads();
+    }
+  }
+
+  t_f32.reduce();
+  t_i8.reduce();
+  t_bf16.reduce();
+  t_lds.reduce();
+  if (lane == 0) {
+    CroCoverageRecord rec;
+    rec.xcc_id = xcc_id;
+    rec.hw_id = hw_id;
+    rec.fail_mask = (t_f32.n_bad ? 1u : 0u) | (t_i8.n_bad ? 2u : 0u) |
+                    (t_bf16.n_bad ? 4u : 0u) | (t_lds.n_bad ? 8u : 0u);
+    rec.n_bad = t_f32.n_bad + t_i8.n_bad + t_bf16.n_bad + t_lds.n_bad;
+    const Tally& lead = t_f32.n_bad ? t_f32 : t_i8.n_bad ? t_i8 : t_bf16.n_bad ? t_bf16 : t_lds;
+    rec.first_bad = lead.first;
+    rec.bits_bad = lead.bits;
+    rec.valid = 1;
+    rec.reserved = 0;
+    p.records[blockIdx.x * kWaves + wave] = rec;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------
+
+double now_ms() {
+  return std::chrono::duration<double, std::milli>(
+             std::chrono::steady_clock::now().time_since_epoch())
+      .count();
+}
+
+// Per-device cached context (as ProbeCtx in probe.hip): inputs and expected
+// tiles are built and uploaded once per device (and again only when the seed
+// changes); the record buffer grows on demand.  The mutex serialises
+// concurrent reconcile workers on one device.
+struct CovCtx {
+  std::mutex mu;
+  int ready = 0;
+  int tiles_ready = 0;
+  uint32_t seed = 0;
+  int cus = 0;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  float *dA32 = nullptr, *dB32 = nullptr, *dE32 = nullptr;
+  int8_t *dA8 = nullptr, *dB8 = nullptr;
+  int* dE8 = nullptr;
+  uint16_t *dA16 = nullptr, *dB16 = nullptr;
+  float* dE16 = nullptr;
+  void* dEx = nullptr;  // self-test mode 1: the altered copy of one expected tile
+  float hE32[CRO_COV_F32_ELEMS];
+  int hE8[CRO_COV_I8_ELEMS];
+  float hE16[CRO_COV_BF16_ELEMS];
+  CroCoverageRecord* d_records = nullptr;
+  size_t records_cap = 0;
+};
+CovCtx g_cctx[64];
+
+#define CCHECK(expr)                                                         \
+  do {                                                                       \
+    hipError_t _e = (expr);                                                  \
+    if (_e != hipSuccess) {                                                  \
+      snprintf(out->msg, sizeof(out->msg), "%s failed: %s", #expr,           \
+               hipGetErrorString(_e));                                       \
+      out->ok = 0;                                                           \
+      out->rc = -1;                                                          \
+      return -1;                                                             \
+    }                                                                        \
+  } while (0)
+
+int bad_arg(CroComputeResult* out, const char* what) {
+  snprintf(out->msg, sizeof(out->msg), "bad argument: %s", what);
+  out->ok = 0;
+  out->rc = -1;
+  return -1;
+}
+
+int upload_tiles(CovCtx* ctx, uint32_t seed, CroComputeResult* out) {
+  static float A32[16 * CRO_COV_F32_K], B32[CRO_COV_F32_K * 16];
+  static int8_t A8[16 * CRO_COV_I8_K], B8[CRO_COV_I8_K * 16];
+  static int Ai[32 * CRO_COV_BF16_K], Bi[CRO_COV_BF16_K * 32];
+  static uint16_t A16[32 * CRO_COV_BF16_K], B16[CRO_COV_BF16_K * 32];
+  static std::mutex build_mu;  // the statics above are shared by all devices
+  std::lock_guard<std::mutex> lock(build_mu);
+  cro_cov_make_f32(seed, A32, B32);
+  cro_cov_ref_f32(A32, B32, ctx->hE32);
+  cro_cov_make_i8(seed, A8, B8);
+  cro_cov_ref_i8(A8, B8, ctx->hE8);
+  cro_cov_make_bf16(seed, Ai, Bi, A16, B16);
+  cro_cov_ref_bf16(Ai, Bi, ctx->hE16);
+  CCHECK(hipMemcpy(ctx->dA32, A32, sizeof(A32), hipMemcpyHostToDevice));
+  CCHECK(hipMemcpy(ctx->dB32, B32, sizeof(B32), hipMemcpyHostToDevice));
+  CCHECK(hipMemcpy(ctx->dE32, ctx->hE32, sizeof(ctx->hE32), hipMemcpyHostToDevice));
+  CCHECK(hipMemcpy(ctx->dA8, A8, sizeof(A8), hipMemcpyHostToDevice));
+  CCHECK(hipMemcpy(ctx->dB8, B8, sizeof(B8), hipMemcpyHostToDevice));
+  CCHECK(hipMemcpy(ctx->dE8, ctx->hE8, sizeof(ctx->hE8), hipMemcpyHostToDevice));
+  CCHECK(hipMemcpy(ctx->dA16, A16, sizeof(A16), hipMemcpyHostToDevice));
+  CCHECK(hipMemcpy(ctx->dB16, B16, sizeof(B16), hipMemcpyHostToDevice));
+  CCHECK(hipMemcpy(ctx->dE16, ctx->hE16, sizeof(ctx->hE16), hipMemcpyHostToDevice));
+  ctx->seed = seed;
+  ctx->tiles_ready = 1;
+  return 0;
+}
+
+int run_compute(int device, const CroComputeOpts* opts, CroComputeResult* out,
+                CroCoverageRecord* records_out, int max_records) {
+  CroComputeOpts o;
+  memset(&o, 0, sizeof(o));
+  if (opts) o = *opts;
+  if (o.grid_blocks < 0 || o.grid_blocks > kMaxGrid) return bad_arg(out, "grid_blocks");
+  if (o.lds_bytes < 0 || o.lds_bytes > CRO_COV_MAX_LDS_BYTES || (o.lds_bytes & 15))
+    return bad_arg(out, "lds_bytes must be a multiple of 16, at most 163840");
+  if (o.iters < 0 || o.iters > kMaxIters) return bad_arg(out, "iters");
+  if (o.max_rounds < 0 || o.max_rounds > kMaxRounds) return bad_arg(out, "max_rounds");
+  if (o.min_cu_fraction < 0.0 || o.min_cu_fraction > 1.0) return bad_arg(out, "min_cu_fraction");
+  const int lds_bytes = o.lds_bytes ? o.lds_bytes : CRO_COV_MAX_LDS_BYTES;
+  const int iters = o.iters ? o.iters : kDefaultIters;
+  const int max_rounds = o.max_rounds ? o.max_rounds : kDefaultRounds;
+  // the self-test only ever names an element that exists: the host indexes
+  // the expected tile with it
+  if (o.selftest_mode < 0 || o.selftest_mode > 2) return bad_arg(out, "selftest_mode");
+  if (o.selftest_mode) {
+    const uint32_t elems[CRO_COV_TESTS] = {CRO_COV_F32_ELEMS, CRO_COV_I8_ELEMS,
+                                           CRO_COV_BF16_ELEMS, (uint32_t)lds_bytes / 4};
+    if (o.selftest_test < 0 || o.selftest_test >= CRO_COV_TESTS)
+      return bad_arg(out, "selftest_test");
+    if (o.selftest_bit < 0 || o.selftest_bit > 31) return bad_arg(out, "selftest_bit");
+    if (o.selftest_elem >= elems[o.selftest_test]) return bad_arg(out, "selftest_elem");
+  }
+
+  int count = 0;
+  CCHECK(hipGetDeviceCount(&count));
+  if (device < 0 || device >= count || device >= 64) {
+    snprintf(out->msg, sizeof(out->msg), "device %d out of range (%d present)", device,
+             count);
+    out->rc = -1;
+    return -1;
+  }
+  CovCtx* ctx = &g_cctx[device];
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  CCHECK(hipSetDevice(device));
+  if (!ctx->ready) {
+    hipDeviceProp_t prop;
+    CCHECK(hipGetDeviceProperties(&prop, device));
+    ctx->cus = prop.multiProcessorCount;
+    CCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(coverage_kernel),
+                               hipFuncAttributeMaxDynamicSharedMemorySize,
+                               CRO_COV_MAX_LDS_BYTES));
+    CCHECK(hipEventCreate(&ctx->e0));
+    CCHECK(hipEventCreate(&ctx->e1));
+    CCHECK(hipMalloc(&ctx->dA32, 16 * CRO_COV_F32_K * sizeof(float)));
+    CCHECK(hipMalloc(&ctx->dB32, CRO_COV_F32_K * 16 * sizeof(float)));
+    CCHECK(hipMalloc(&ctx->dE32, sizeof(ctx->hE32)));
+    CCHECK(hipMalloc(&ctx->dA8, 16 * CRO_COV_I8_K));
+    CCHECK(hipMalloc(&ctx->dB8, CRO_COV_I8_K * 16));
+    CCHECK(hipMalloc(&ctx->dE8, sizeof(ctx->hE8)));
+    CCHECK(hipMalloc(&ctx->dA16, 32 * CRO_COV_BF16_K * sizeof(uint16_t)));
+    CCHECK(hipMalloc(&ctx->dB16, CRO_COV_BF16_K * 32 * sizeof(uint16_t)));
+    CCHECK(hipMalloc(&ctx->dE16, sizeof(ctx->hE16)));
+    CCHECK(hipMalloc(&ctx->dEx, sizeof(ctx->hE16)));  // the largest tile
+    ctx->ready = 1;
+  }
+  if (!ctx->tiles_ready || ctx->seed != o.seed) {
+    ctx->tiles_ready = 0;
+    if (upload_tiles(ctx, o.seed, out) != 0) return -1;
+  }
+  const int grid = o.grid_blocks ? o.grid_blocks : ctx->cus;
+  if (grid < 1) return bad_arg(out, "device reports no compute units");
+  const size_t per_round = (size_t)grid * kWaves;
+  const size_t n_max = per_round * (size_t)max_rounds;
+  if (ctx->records_cap < n_max) {
+    if (ctx->d_records) (void)hipFree(ctx->d_records);
+    ctx->d_records = nullptr;
+    ctx->records_cap = 0;
+    CCHECK(hipMalloc(&ctx->d_records, n_max * sizeof(CroCoverageRecord)));
+    ctx->records_cap = n_max;
+  }
+  out->cus_expected = ctx->cus;
+  out->grid_blocks = grid;
+  out->lds_bytes = lds_bytes;
+  out->iters = iters;
+
+  CovParams p;
+  p.A32 = ctx->dA32;
+  p.B32 = ctx->dB32;
+  p.E32 = ctx->dE32;
+  p.A8 = ctx->dA8;
+  p.B8 = ctx->dB8;
+  p.E8 = ctx->dE8;
+  p.A16 = ctx->dA16;
+  p.B16 = ctx->dB16;
+  p.E16 = ctx->dE16;
+  p.lds_words = (uint32_t)lds_bytes / 4;
+  p.iters = (uint32_t)iters;
+  p.seed = o.seed;
+  p.inj_mode = (uint32_t)o.selftest_mode;
+  p.inj_test = (uint32_t)o.selftest_test;
+  p.inj_elem = o.selftest_elem;
+  p.inj_flip = 1u << (o.selftest_bit & 31);
+  p.inj_key = o.selftest_key;
+  if (o.selftest_mode == 1 && o.selftest_test != CRO_COV_TEST_LDS) {
+    // flip one bit of one expected element in a copy; the cached tile stays
+    uint32_t alt[CRO_COV_BF16_ELEMS];
+    size_t bytes = 0;
+    if (o.selftest_test == CRO_COV_TEST_F32) {
+      bytes = sizeof(ctx->hE32);
+      memcpy(alt, ctx->hE32, bytes);
+      p.E32 = (const float*)ctx->dEx;
+    } else if (o.selftest_test == CRO_COV_TEST_I8) {
+      bytes = sizeof(ctx->hE8);
+      memcpy(alt, ctx->hE8, bytes);
+      p.E8 = (const int*)ctx->dEx;
+    } else {
+      bytes = sizeof(ctx->hE16);
+      memcpy(alt, ctx->hE16, bytes);
+      p.E16 = (const float*)ctx->dEx;
+    }
+    alt[o.selftest_elem] ^= p.inj_flip;
+    CCHECK(hipMemcpy(ctx->dEx, alt, bytes, hipMemcpyHostToDevice));
+  }
+
+  std::vector<CroCoverageRecord> records(n_max);
+  CCHECK(hipMemset(ctx->d_records, 0, n_max * sizeof(CroCoverageRecord)));
+  int rounds = 0;
+  double gpu_ms = 0.0;
+  for (;;) {
+    p.records = ctx->d_records + (size_t)rounds * per_round;
+    CCHECK(hipEventRecord(ctx->e0));
+    hipLaunchKernelGGL(coverage_kernel, dim3(grid), dim3(kBlock), (size_t)lds_bytes, 0, p);
+    CCHECK(hipGetLastError());
+    CCHECK(hipEventRecord(ctx->e1));
+    CCHECK(hipEventSynchronize(ctx->e1));
+    float ms = 0.f;
+    CCHECK(hipEventElapsedTime(&ms, ctx->e0, ctx->e1));
+    gpu_ms += ms;
+    CCHECK(hipMemcpy(records.data() + (size_t)rounds * per_round, p.records,
+                     per_round * sizeof(CroCoverageRecord), hipMemcpyDeviceToHost));
+    ++rounds;
+    cro_coverage_aggregate(records.data(), (size_t)rounds * per_round, ctx->cus, &out->agg);
+    const bool covered =
+        out->agg.cus_seen >= ctx->cus && out->agg.simds_seen >= 4 * out->agg.cus_seen;
+    if (out->agg.waves_bad || covered || rounds >= max_rounds) break;
+  }
+  out->rounds = rounds;
+  out->gpu_ms = gpu_ms;
+  const size_t n = (size_t)rounds * per_round;
+  if (records_out && max_records > 0) {
+    const size_t m = n < (size_t)max_records ? n : (size_t)max_records;
+    memcpy(records_out, records.data(), m * sizeof(CroCoverageRecord));
+  }
+  const CroCoverageAgg& a = out->agg;
+  if (a.waves_run != n) {
+    // a wave that never wrote its record: the launch did not run to the end
+    out->rc = -1;
+    snprintf(out->msg, sizeof(out->msg), "%llu of %zu waves reported", a.waves_run, n);
+    return -1;
+  }
+  if (a.waves_bad) {
+    out->rc = -30;
+    out->first_bad_round = (int)((size_t)a.first_bad_index / per_round);
+    out->first_bad_record = (int)((size_t)a.first_bad_index % per_round);
+    snprintf(out->failed_test, sizeof(out->failed_test), "%s",
+             cro_cov_test_name(a.first_fail_mask));
+    snprintf(out->msg, sizeof(out->msg),
+             "compute mismatch in %s at xcd=%d se=%d sh=%d cu=%d simd=%d: element %u, "
+             "bits 0x%08x; %llu of %llu waves bad on %d CUs",
+             out->failed_test, a.xcd, a.se, a.sh, a.cu, a.simd, a.first_bad, a.bits_bad,
+             a.waves_bad, a.waves_run, a.cus_bad);
+    return -30;
+  }
+  if (o.min_cu_fraction > 0.0 && (double)a.cus_seen < o.min_cu_fraction * (double)ctx->cus) {
+    out->rc = -31;
+    snprintf(out->msg, sizeof(out->msg),
+             "coverage %d of %d CUs after %d rounds is below the floor %.3f", a.cus_seen,
+             ctx->cus, rounds, o.min_cu_fraction);
+    return -31;
+  }
+  out->ok = 1;
+  snprintf(out->msg, sizeof(out->msg), "ok");
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int cro_probe_compute_records(int device, const struct CroComputeOpts* opts,
+                                         struct CroComputeResult* out,
+                                         struct CroCoverageRecord* records_out,
+                                         int max_records) {
+  memset(out, 0, sizeof(*out));
+  out->first_bad_round = out->first_bad_record = -1;
+  out->agg.first_bad_index = -1;
+  out->agg.xcd = out->agg.se = out->agg.sh = out->agg.cu = out->agg.simd = -1;
+  out->agg.first_bad = ~0u;
+  const double t0 = now_ms();
+  const int rc = run_compute(device, opts, out, records_out, max_records);
+  out->t_total_ms = now_ms() - t0;
+  return rc;
+}
+
+extern "C" int cro_probe_compute(int device, const struct CroComputeOpts* opts,
+                                 struct CroComputeResult* out) {
+  return cro_probe_compute_records(device, opts, out, nullptr, 0);
+}
+
+extern "C" int cro_probe_mfma_tile(int device, int kind, const void* A, const void* B,
+                                   void* D, int K) {
+  if (kind != 1 && kind != 2) return -10;
+  const int step = kind == 1 ? 64 : 16;
+  if (A == nullptr || B == nullptr || D == nullptr) return -10;
+  if (K <= 0 || K > kMaxTileK || K % step != 0) return -10;
+  const int rows = kind == 1 ? 16 : 32;
+  const size_t esz = kind == 1 ? 1 : 2;
+  const size_t in_bytes = (size_t)rows * K * esz, out_bytes = (size_t)rows * rows * 4;
+  if (hipSetDevice(device) != hipSuccess) return -1;
+  void *dA = nullptr, *dB = nullptr, *dD = nullptr;
+  hipError_t e = hipMalloc(&dA, in_bytes);
+  if (e == hipSuccess) e = hipMalloc(&dB, in_bytes);
+  if (e == hipSuccess) e = hipMalloc(&dD, out_bytes);
+  if (e == hipSuccess) e = hipMemcpy(dA, A, in_bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dB, B, in_bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(mfma_tile_kernel, dim3(1), dim3(64), 0, 0, kind, dA, dB, dD, K);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(D, dD, out_bytes, hipMemcpyDeviceToHost);
+  if (dA) (void)hipFree(dA);
+  if (dB) (void)hipFree(dB);
+  if (dD) (void)hipFree(dD);
+  return e == hipSuccess ? 0 : -1;
+}

@@ -1,8 +1,10 @@
 // Shared C ABI for the gfx950 health probe library (libcroprobe.so).
-// Consumers: probe.hip and integrity.hip (implementation),
+// Consumers: probe.hip, integrity.hip and coverage.hip (implementation),
 // agent/croagent.cpp (native CLI),
 // nodeops/probe.py (ctypes — keep CroProbeResult field order in sync there).
 #pragma once
+
+#include "crocoverage.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -89,6 +91,66 @@ int cro_probe_pattern_verify(int device, unsigned int seed, int invert,
                              unsigned long long base_word, unsigned long long n_words,
                              const unsigned int* host_in, unsigned long long* n_bad,
                              unsigned long long* first_bad, unsigned int* bits_bad);
+
+// -- compute-coverage stage: exact checks on every CU and SIMD, with fault
+// location (coverage.hip; record, decode and aggregate in crocoverage.h).
+// nodeops/probe.py mirrors both structs with ctypes — keep field order in
+// sync there (tests/test_probe_compute.py compares sizeof/offsetof).
+
+struct CroComputeOpts {
+  int grid_blocks;  // 0 → multiProcessorCount
+  int lds_bytes;    // 0 → 163840 (a CU's whole LDS: one workgroup per CU);
+                    // a multiple of 16, at most 163840
+  int iters;        // 0 → 16 (≈0.6 ms; profiles/compute_probe_mi355x.md); repeats
+                    // of all four checks per wave
+  int max_rounds;   // 0 → 4; launches while some CU or SIMD is still unseen
+  unsigned int seed;  // 0 is a valid seed
+  // Self-test, for tests only: shows detection and localisation through data
+  // alone.  Mode 1: the host flips bit selftest_bit of element selftest_elem
+  // in the EXPECTED tile of test selftest_test (0 f32, 1 i8, 2 bf16, 3 LDS)
+  // before upload; every wave must flag it.  Mode 2: the kernel flips that
+  // bit in its COMPUTED value on the waves whose CU key is selftest_key;
+  // exactly those waves may flag it.  For the LDS test, where each word is
+  // checked by one wave only, the flip is repeated at the same lane and trip
+  // of all four waves of a workgroup.
+  int selftest_mode;
+  int selftest_test;
+  int selftest_bit;
+  unsigned int selftest_elem;
+  unsigned int selftest_key;
+  double min_cu_fraction;  // 0 = off; else fail when cus_seen / cus_expected is below
+};
+
+struct CroComputeResult {
+  int ok;
+  int rc;  // 0 ok, -1 HIP error or bad argument, -30 compute mismatch, -31 coverage floor
+  int cus_expected;  // hipDeviceProp_t::multiProcessorCount
+  int rounds;        // launches of the grid
+  struct CroCoverageAgg agg;  // over all rounds
+  int first_bad_round;   // of the first bad wave; -1 = none
+  int first_bad_record;  // workgroup * 4 + wave within that round; -1 = none
+  int grid_blocks;       // as run
+  int lds_bytes;
+  int iters;
+  int reserved;
+  double gpu_ms;      // event-timed, summed over the rounds
+  double t_total_ms;  // host wall
+  char failed_test[16];  // "", "mfma_f32", "mfma_i8", "mfma_bf16", "lds"
+  char msg[256];
+};
+
+int cro_probe_compute(int device, const struct CroComputeOpts* opts,
+                      struct CroComputeResult* out);
+// The same, and copies out the raw records (rounds * grid_blocks * 4 of them,
+// round-major) up to max_records, for tests.
+int cro_probe_compute_records(int device, const struct CroComputeOpts* opts,
+                              struct CroComputeResult* out,
+                              struct CroCoverageRecord* records_out, int max_records);
+// Raw tile entry for the lane-map tests, one wave of the coverage kernel's
+// body on caller data.  kind 1: i8, A 16xK, B Kx16 (int8), D 16x16 (int32),
+// K a multiple of 64.  kind 2: bf16, A 32xK, B Kx32 (bf16 bit patterns),
+// D 32x32 (float), K a multiple of 16.  Row-major; K at most 4096.
+int cro_probe_mfma_tile(int device, int kind, const void* A, const void* B, void* D, int K);
 
 #ifdef __cplusplus
 }

@@ -2,8 +2,11 @@
 //
 // The MI355X-native replacement for the reference's "is the GPU alive"
 // signal (forking `nvidia-smi` over pod exec, gpus.go:207-350): after the
-// fabric composes a device and amdgpu binds it, this probe verifies the
-// silicon actually computes before the operator advertises it via CDI:
+// fabric composes a device and amdgpu binds it, this probe checks that the
+// device computes and streams at the expected rates before the operator
+// advertises it via CDI.  The exact check runs on ONE wave on one CU and
+// the rate kernels compare nothing: every CU and SIMD is checked exactly
+// only by the opt-in compute-coverage stage (coverage.hip).
 //
 //   1. mfma_f32_check  — one wave issues v_mfma_f32_16x16x4_f32 over a
 //      K-loop; gfx950's f32-input MFMA is bitwise a k-ordered fmaf chain,

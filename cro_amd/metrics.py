@@ -74,6 +74,13 @@ class Metrics:
             "d2h_kernel)",
             ["stage"],
         )
+        self.probe_compute_failures_total = Counter(
+            "cro_probe_compute_failures_total",
+            "Attaches refused by the probe's compute-coverage stage, by the "
+            "check that failed (mfma_f32, mfma_i8, mfma_bf16, lds; coverage "
+            "for the optional CU-coverage floor)",
+            ["test"],
+        )
 
     # test helper: drop collectors so a fresh interpreter state can be faked
     @classmethod
@@ -87,6 +94,7 @@ class Metrics:
                 cls._singleton.fabric_request_seconds,
                 cls._singleton.devices_online,
                 cls._singleton.probe_integrity_failures_total,
+                cls._singleton.probe_compute_failures_total,
             ):
                 try:
                     REGISTRY.unregister(collector)

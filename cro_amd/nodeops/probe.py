@@ -83,6 +83,79 @@ class CroIntegrityResult(ctypes.Structure):
     )
 
 
+class CroComputeOpts(ctypes.Structure):
+    """Mirror of ``struct CroComputeOpts`` (cro_amd/hip/croprobe.h)."""
+
+    _fields_ = [
+        ("grid_blocks", ctypes.c_int),
+        ("lds_bytes", ctypes.c_int),
+        ("iters", ctypes.c_int),
+        ("max_rounds", ctypes.c_int),
+        ("seed", ctypes.c_uint),
+        ("selftest_mode", ctypes.c_int),
+        ("selftest_test", ctypes.c_int),
+        ("selftest_bit", ctypes.c_int),
+        ("selftest_elem", ctypes.c_uint),
+        ("selftest_key", ctypes.c_uint),
+        ("min_cu_fraction", ctypes.c_double),
+    ]
+
+
+class CroCoverageRecord(ctypes.Structure):
+    """Mirror of ``struct CroCoverageRecord`` (cro_amd/hip/crocoverage.h)."""
+
+    _fields_ = [
+        ("xcc_id", ctypes.c_uint),
+        ("hw_id", ctypes.c_uint),
+        ("fail_mask", ctypes.c_uint),
+        ("n_bad", ctypes.c_uint),
+        ("first_bad", ctypes.c_uint),
+        ("bits_bad", ctypes.c_uint),
+        ("valid", ctypes.c_uint),
+        ("reserved", ctypes.c_uint),
+    ]
+
+
+COMPUTE_TESTS = ("mfma_f32", "mfma_i8", "mfma_bf16", "lds")
+# fields of the nested ``struct CroCoverageAgg`` (crocoverage.h), in order
+COMPUTE_AGG_FIELDS = (
+    [(n, ctypes.c_ulonglong) for n in
+     ("waves_run", "waves_bad", "bad_f32", "bad_i8", "bad_bf16", "bad_lds")]
+    + [("first_bad_index", ctypes.c_longlong)]
+    + [(n, ctypes.c_int) for n in
+       ("cus_seen", "xcds_seen", "simds_seen", "cus_bad", "xcd", "se", "sh", "cu", "simd")]
+    + [(n, ctypes.c_uint) for n in ("first_fail_mask", "n_bad", "first_bad", "bits_bad")]
+    + [("n_bad_cu_keys", ctypes.c_int), ("bad_cu_keys", ctypes.c_uint * 8)]
+)
+
+
+class CroComputeResult(ctypes.Structure):
+    """Mirror of ``struct CroComputeResult`` (cro_amd/hip/croprobe.h), with
+    the nested aggregate's fields written out flat."""
+
+    _fields_ = (
+        [
+            ("ok", ctypes.c_int),
+            ("rc", ctypes.c_int),
+            ("cus_expected", ctypes.c_int),
+            ("rounds", ctypes.c_int),
+        ]
+        + COMPUTE_AGG_FIELDS
+        + [
+            ("first_bad_round", ctypes.c_int),
+            ("first_bad_record", ctypes.c_int),
+            ("grid_blocks", ctypes.c_int),
+            ("lds_bytes", ctypes.c_int),
+            ("iters", ctypes.c_int),
+            ("reserved", ctypes.c_int),
+            ("gpu_ms", ctypes.c_double),
+            ("t_total_ms", ctypes.c_double),
+            ("failed_test", ctypes.c_char * 16),
+            ("msg", ctypes.c_char * 256),
+        ]
+    )
+
+
 PROBE_LEVELS = ("quick", "deep")
 
 _lib = None
@@ -135,6 +208,20 @@ def load_library(required: Optional[bool] = None) -> Optional[ctypes.CDLL]:
         ctypes.c_ulonglong, ctypes.c_ulonglong, u32p, u64p, u64p, u32p,
     ]
     lib.cro_probe_pattern_verify.restype = ctypes.c_int
+    lib.cro_probe_compute.argtypes = [
+        ctypes.c_int, ctypes.POINTER(CroComputeOpts), ctypes.POINTER(CroComputeResult),
+    ]
+    lib.cro_probe_compute.restype = ctypes.c_int
+    lib.cro_probe_compute_records.argtypes = [
+        ctypes.c_int, ctypes.POINTER(CroComputeOpts), ctypes.POINTER(CroComputeResult),
+        ctypes.POINTER(CroCoverageRecord), ctypes.c_int,
+    ]
+    lib.cro_probe_compute_records.restype = ctypes.c_int
+    lib.cro_probe_mfma_tile.argtypes = [
+        ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_int,
+    ]
+    lib.cro_probe_mfma_tile.restype = ctypes.c_int
     _lib = lib
     return lib
 
@@ -287,39 +374,306 @@ def pattern_verify(device: int, seed: int, invert, base_word: int, words) -> dic
     return {"n_bad": n_bad.value, "first_bad": first_bad.value, "bits_bad": bits_bad.value}
 
 
+# -- compute-coverage stage (cro_amd/hip/coverage.hip) ----------------------------
+
+
+def _compute_dict(res: "CroComputeResult", rc: int) -> dict:
+    out = {"ok": bool(res.ok) and rc == 0, "rc": rc}
+    for name, _ in CroComputeResult._fields_[2:]:
+        value = getattr(res, name)
+        if name == "bad_cu_keys":
+            value = [int(k) for k in value][: res.n_bad_cu_keys]
+        elif isinstance(value, bytes):
+            value = value.decode(errors="replace")
+        out[name] = value
+    del out["reserved"]
+    return out
+
+
+def _compute_opts(grid_blocks=0, lds_bytes=0, iters=0, max_rounds=0, seed=0,
+                  min_cu_fraction=0.0, selftest_mode=0, selftest_test=0, selftest_elem=0,
+                  selftest_bit=0, selftest_key=0) -> "CroComputeOpts":
+    if isinstance(selftest_test, str):
+        selftest_test = COMPUTE_TESTS.index(selftest_test)
+    return CroComputeOpts(
+        grid_blocks=int(grid_blocks), lds_bytes=int(lds_bytes), iters=int(iters),
+        max_rounds=int(max_rounds), seed=int(seed) & 0xFFFFFFFF,
+        selftest_mode=int(selftest_mode), selftest_test=int(selftest_test),
+        selftest_bit=int(selftest_bit), selftest_elem=int(selftest_elem),
+        selftest_key=int(selftest_key), min_cu_fraction=float(min_cu_fraction),
+    )
+
+
+def run_compute(device: int = 0, **opts) -> dict:
+    """Compute-coverage stage: exact f32, i8 and bf16 matrix checks and an LDS
+    march on every CU and SIMD, with the location of the first bad wave
+    (cro_amd/hip/coverage.hip).  Options as ``struct CroComputeOpts``; zero
+    takes the library default.  A data mismatch always fails; coverage is
+    reported and gates only when ``min_cu_fraction`` > 0.  The ``selftest_*``
+    options are for tests."""
+    lib = load_library(required=True)
+    c_opts = _compute_opts(**opts)
+    res = CroComputeResult()
+    rc = lib.cro_probe_compute(device, ctypes.byref(c_opts), ctypes.byref(res))
+    return _compute_dict(res, rc)
+
+
+def run_compute_records(device: int = 0, **opts):
+    """As run_compute, and returns the raw per-wave records as well: a
+    structured numpy array of rounds * grid_blocks * 4 records, round-major."""
+    import numpy as np
+
+    lib = load_library(required=True)
+    c_opts = _compute_opts(**opts)
+    res = CroComputeResult()
+    # room for what was asked; a default grid is one workgroup per CU, and
+    # no device of this family has more than 1024 of them
+    blocks = c_opts.grid_blocks or 1024
+    rounds = c_opts.max_rounds or 4
+    cap = max(blocks * 4 * rounds, 1)
+    buf = (CroCoverageRecord * cap)()
+    rc = lib.cro_probe_compute_records(device, ctypes.byref(c_opts), ctypes.byref(res), buf, cap)
+    out = _compute_dict(res, rc)
+    n = min(out["rounds"] * out["grid_blocks"] * 4, cap)
+    dtype = np.dtype([(name, np.uint32) for name, _ in CroCoverageRecord._fields_])
+    records = np.frombuffer(buf, dtype=dtype, count=cap)[:n].copy()
+    return out, records
+
+
+MFMA_TILE_KINDS = {"i8": 1, "bf16": 2}
+
+
+def bf16_bits(values):
+    """bf16 bit patterns (uint16) of float32 values that bf16 holds exactly."""
+    import numpy as np
+
+    u = np.ascontiguousarray(values, dtype=np.float32).view(np.uint32)
+    if np.any(u & np.uint32(0xFFFF)):
+        raise ValueError("value not exactly representable in bf16")
+    return (u >> np.uint32(16)).astype(np.uint16)
+
+
+def mfma_tile(device: int, kind: str, a, b):
+    """One wave of the coverage kernel's i8 (16xK @ Kx16 → int32 16x16) or
+    bf16 (32xK @ Kx32 → float32 32x32; inputs given as numbers bf16 holds
+    exactly) matrix product on caller data."""
+    import numpy as np
+
+    lib = load_library(required=True)
+    rows = 16 if kind == "i8" else 32
+    a = np.asarray(a)
+    b = np.asarray(b)
+    k = a.shape[1]
+    if a.shape != (rows, k) or b.shape != (k, rows):
+        raise ValueError(f"{kind} tile wants A {rows}xK and B Kx{rows}")
+    if kind == "i8":
+        a_dev = np.ascontiguousarray(a, dtype=np.int8)
+        b_dev = np.ascontiguousarray(b, dtype=np.int8)
+        d = np.zeros((rows, rows), dtype=np.int32)
+    else:
+        a_dev, b_dev = bf16_bits(a), bf16_bits(b)
+        d = np.zeros((rows, rows), dtype=np.float32)
+    rc = lib.cro_probe_mfma_tile(
+        device, MFMA_TILE_KINDS[kind], a_dev.ctypes.data, b_dev.ctypes.data, d.ctypes.data, k
+    )
+    if rc != 0:
+        raise RuntimeError(f"cro_probe_mfma_tile failed: rc={rc}")
+    return d
+
+
+def _lcg_stream(state: int, n: int):
+    """n steps of the probe's LCG (probe.hip, crocoverage.h) from ``state``."""
+    import numpy as np
+
+    out = np.empty(n, dtype=np.uint32)
+    for i in range(n):
+        state = (state * 1664525 + 1013904223) & 0xFFFFFFFF
+        out[i] = state
+    return out, state
+
+
+def compute_inputs(seed: int = 0) -> dict:
+    """numpy mirror of the compute stage's inputs (crocoverage.h): f32
+    A 16x64 / B 64x16, i8 A 16x256 / B 256x16, bf16 A 32x64 / B 64x32 (as the
+    integers the bf16 values hold)."""
+    import numpy as np
+
+    seed &= 0xFFFFFFFF
+    raw, state = _lcg_stream(0x9E3779B9 ^ seed, 16 * 64)
+    a32 = ((raw >> np.uint32(8)).astype(np.float32) / np.float32(16777216.0)) - np.float32(0.5)
+    raw, _ = _lcg_stream(state, 64 * 16)
+    b32 = ((raw >> np.uint32(8)).astype(np.float32) / np.float32(16777216.0)) - np.float32(0.5)
+    raw, state = _lcg_stream(0x85EBCA6B ^ seed, 16 * 256)
+    a8 = (raw >> np.uint32(24)).astype(np.uint8).view(np.int8).copy()
+    raw, _ = _lcg_stream(state, 256 * 16)
+    b8 = (raw >> np.uint32(24)).astype(np.uint8).view(np.int8).copy()
+    a8[0], a8[1], b8[0], b8[16] = -128, 127, -128, 127
+
+    def small(raw):
+        mag = 1 + ((raw >> np.uint32(28)) & np.uint32(7)).astype(np.int32)
+        return np.where((raw >> np.uint32(27)) & np.uint32(1), -mag, mag).astype(np.int32)
+
+    raw, state = _lcg_stream(0xC2B2AE35 ^ seed, 32 * 64)
+    a16 = small(raw)
+    raw, _ = _lcg_stream(state, 64 * 32)
+    b16 = small(raw)
+    return {
+        "f32": (a32.reshape(16, 64), b32.reshape(64, 16)),
+        "i8": (a8.reshape(16, 256), b8.reshape(256, 16)),
+        "bf16": (a16.reshape(32, 64), b16.reshape(64, 32)),
+    }
+
+
+def compute_expected_tiles(seed: int = 0) -> dict:
+    """numpy mirror of the three expected tiles.  f32 is the k-ordered fmaf
+    chain: the product of two float32 is exact in float64 and the sum is
+    rounded once to float64 before the rounding to float32, which differs
+    from a true fused multiply-add only when the float64 sum lands exactly on
+    a float32 tie — the CPU test compares this tile with the header's."""
+    import numpy as np
+
+    inputs = compute_inputs(seed)
+    a32, b32 = inputs["f32"]
+    acc = np.zeros((16, 16), dtype=np.float32)
+    for k in range(a32.shape[1]):
+        prod = a32[:, k : k + 1].astype(np.float64) * b32[k : k + 1, :].astype(np.float64)
+        acc = (prod + acc.astype(np.float64)).astype(np.float32)
+    a8, b8 = inputs["i8"]
+    a16, b16 = inputs["bf16"]
+    return {
+        "f32": acc,
+        "i8": a8.astype(np.int32) @ b8.astype(np.int32),
+        "bf16": (a16 @ b16).astype(np.float32),
+    }
+
+
+def cu_key(xcc_id, hw_id):
+    """(XCD, SE, SH, CU) of a record in one word (cro_cov_cu_key)."""
+    return ((xcc_id & 0xF) << 16) | (hw_id & 0xFF00)
+
+
+def decode_location(xcc_id, hw_id) -> dict:
+    """numpy/int mirror of cro_cov_decode: HW_ID fields WAVE_ID 3:0,
+    SIMD_ID 5:4, CU_ID 11:8, SH_ID 12, SE_ID 15:13; XCC_ID 3:0."""
+    return {
+        "xcd": xcc_id & 0xF,
+        "se": (hw_id >> 13) & 0x7,
+        "sh": (hw_id >> 12) & 0x1,
+        "cu": (hw_id >> 8) & 0xF,
+        "simd": (hw_id >> 4) & 0x3,
+        "wave_slot": hw_id & 0xF,
+    }
+
+
+def decode_cu_key(key) -> dict:
+    loc = decode_location(key >> 16, key & 0xFF00)
+    return {k: loc[k] for k in ("xcd", "se", "sh", "cu")}
+
+
+def aggregate_records(records) -> dict:
+    """numpy mirror of cro_coverage_aggregate over a structured record array
+    (or any mapping of equal-length uint32 arrays)."""
+    import numpy as np
+
+    valid = np.asarray(records["valid"]) != 0
+    xcc = np.asarray(records["xcc_id"])[valid].astype(np.int64)
+    hw = np.asarray(records["hw_id"])[valid].astype(np.int64)
+    mask = np.asarray(records["fail_mask"])[valid].astype(np.int64)
+    keys = cu_key(xcc, hw)
+    simd = (hw >> 4) & 0x3
+    bad = mask != 0
+    bad_keys = []
+    for key in keys[bad]:
+        if int(key) not in bad_keys:
+            bad_keys.append(int(key))
+    out = {
+        "waves_run": int(valid.sum()),
+        "waves_bad": int(bad.sum()),
+        "bad_f32": int(((mask & 1) != 0).sum()),
+        "bad_i8": int(((mask & 2) != 0).sum()),
+        "bad_bf16": int(((mask & 4) != 0).sum()),
+        "bad_lds": int(((mask & 8) != 0).sum()),
+        "first_bad_index": -1,
+        "cus_seen": int(np.unique(keys).size),
+        "xcds_seen": int(np.unique(xcc & 0xF).size),
+        "simds_seen": int(np.unique(keys * 4 + simd).size),
+        "cus_bad": len(bad_keys),
+        "xcd": -1, "se": -1, "sh": -1, "cu": -1, "simd": -1,
+        "first_fail_mask": 0, "n_bad": 0, "first_bad": 0xFFFFFFFF, "bits_bad": 0,
+        "n_bad_cu_keys": min(len(bad_keys), 8),
+        "bad_cu_keys": bad_keys[:8],
+    }
+    if bad.any():
+        first = int(np.flatnonzero(valid)[np.flatnonzero(bad)[0]])
+        loc = decode_location(int(records["xcc_id"][first]), int(records["hw_id"][first]))
+        out.update({k: int(loc[k]) for k in ("xcd", "se", "sh", "cu", "simd")})
+        out.update(
+            first_bad_index=first,
+            first_fail_mask=int(records["fail_mask"][first]),
+            n_bad=int(records["n_bad"][first]),
+            first_bad=int(records["first_bad"][first]),
+            bits_bad=int(records["bits_bad"][first]),
+        )
+    return out
+
+
 def make_probe_fn(level: str = "quick", vram_bytes: int = 0, link_bytes: int = 0,
-                  link_floor_gbps: float = 0.0, seed: int = 0):
+                  link_floor_gbps: float = 0.0, seed: int = 0, compute: bool = False,
+                  compute_min_cu_fraction: float = 0.0):
     """AmdNodeOps probe hook for a probe level.
 
     ``quick`` is the rate/matrix-pipe gate.  ``deep`` runs it first and, only
     when it passed (a device that failed the quick gate is not stressed
     further), the data-integrity stage on the same ordinal; the result nests
     under ``"integrity"`` and ``ok`` is the AND of both.
-    """
-    if level == "quick":
-        return probe_fn_for_nodeops
-    if level != "deep":
-        raise ValueError(f"unknown probe level {level!r} (expected one of {PROBE_LEVELS})")
 
-    def deep_probe(gpu) -> dict:
+    ``compute=True`` adds the compute-coverage stage to either level, between
+    the two: quick, then compute, then (``deep``) integrity, stopping at the
+    first stage that fails.  Its result nests under ``"compute"``; ``ok`` is
+    the AND of the stages run and ``msg`` the failing stage's.
+    """
+    if level not in PROBE_LEVELS:
+        raise ValueError(f"unknown probe level {level!r} (expected one of {PROBE_LEVELS})")
+    if level == "quick" and not compute:
+        return probe_fn_for_nodeops
+
+    def staged_probe(gpu) -> dict:
         dev = hip_device_for_bdf(gpu.pci_bdf)
         if dev is None:
             dev = 0
         result = run_probe(dev)
         if not result.get("ok"):
             return result
-        integrity = run_integrity(
-            dev, vram_bytes=vram_bytes, link_bytes=link_bytes, seed=seed,
-            link_floor_gbps=link_floor_gbps,
-        )
-        result["integrity"] = integrity
-        if not integrity.get("ok"):
-            result["ok"] = False
-            result["msg"] = integrity.get("msg", "integrity probe failed")
+        if compute:
+            stage = run_compute(dev, seed=seed, min_cu_fraction=compute_min_cu_fraction)
+            result["compute"] = stage
+            if not stage.get("ok"):
+                result["ok"] = False
+                result["msg"] = stage.get("msg", "compute probe failed")
+                return result
+        if level == "deep":
+            integrity = run_integrity(
+                dev, vram_bytes=vram_bytes, link_bytes=link_bytes, seed=seed,
+                link_floor_gbps=link_floor_gbps,
+            )
+            result["integrity"] = integrity
+            if not integrity.get("ok"):
+                result["ok"] = False
+                result["msg"] = integrity.get("msg", "integrity probe failed")
         return result
 
-    deep_probe.level = "deep"
-    return deep_probe
+    staged_probe.level = level
+    staged_probe.compute = bool(compute)
+    return staged_probe
+
+
+def _compute_argv(compute, compute_min_cu_fraction) -> list:
+    if not compute:
+        return []
+    argv = ["--compute"]
+    if compute_min_cu_fraction:
+        argv += ["--compute-min-cu-fraction", str(float(compute_min_cu_fraction))]
+    return argv
 
 
 def _deep_argv(level: str, vram_mib, link_mib, link_floor_gbps) -> list:
@@ -338,12 +692,14 @@ def _deep_argv(level: str, vram_mib, link_mib, link_floor_gbps) -> list:
 
 
 def probe_via_exec(execer, node: str, gpu, argv_prefix=None, level: str = "quick",
-                   vram_mib=None, link_mib=None, link_floor_gbps=0) -> dict:
+                   vram_mib=None, link_mib=None, link_floor_gbps=0, compute: bool = False,
+                   compute_min_cu_fraction=0) -> dict:
     """Health probe through the node agent (``croagent probe --bdf``) — the
     cluster shape where controllers run off-node and reach hardware only
     through the NodeExec seam.  Returns the same dict shape as run_probe
     (at level ``deep``: as make_probe_fn("deep"), via ``croagent probe
-    --deep`` and the size options given).
+    --deep`` and the size options given; with ``compute``: as
+    make_probe_fn(..., compute=True), via ``--compute``).
 
     ``argv_prefix`` wraps the command for the container-driver arm (e.g.
     ``["chroot", "/run/amdgpu-driver"]`` so the probe runs against the
@@ -354,6 +710,7 @@ def probe_via_exec(execer, node: str, gpu, argv_prefix=None, level: str = "quick
 
     argv = list(argv_prefix or []) + ["croagent", "probe", "--bdf", gpu.pci_bdf]
     argv += _deep_argv(level, vram_mib, link_mib, link_floor_gbps)
+    argv += _compute_argv(compute, compute_min_cu_fraction)
     rc, out, err = execer.run(node, argv, timeout=300)
     if rc != 0 and not out.strip():
         return {"ok": False, "rc": rc, "msg": err.strip() or "croagent probe failed"}
@@ -364,7 +721,8 @@ def probe_via_exec(execer, node: str, gpu, argv_prefix=None, level: str = "quick
 
 
 def make_exec_probe_fn(execer, node: str, argv_prefix_fn=None, level: str = "quick",
-                       vram_mib=None, link_mib=None, link_floor_gbps=0):
+                       vram_mib=None, link_mib=None, link_floor_gbps=0, compute: bool = False,
+                       compute_min_cu_fraction=0):
     """AmdNodeOps probe hook bound to a NodeExec (local or remote agent).
 
     ``argv_prefix_fn()`` is resolved per probe so a driver-mode change
@@ -377,7 +735,8 @@ def make_exec_probe_fn(execer, node: str, argv_prefix_fn=None, level: str = "qui
         prefix = argv_prefix_fn() if argv_prefix_fn else None
         return probe_via_exec(
             execer, node, gpu, argv_prefix=prefix, level=level, vram_mib=vram_mib,
-            link_mib=link_mib, link_floor_gbps=link_floor_gbps,
+            link_mib=link_mib, link_floor_gbps=link_floor_gbps, compute=compute,
+            compute_min_cu_fraction=compute_min_cu_fraction,
         )
 
     return probe
