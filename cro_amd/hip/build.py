@@ -28,6 +28,9 @@ OUT = os.path.join(HIP_DIR, "libcroprobe.so")
 AGENT_SRC = os.path.join(AGENT_DIR, "croagent.cpp")
 AGENT_OUT = os.path.join(AGENT_DIR, "croagent")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+# the library's device compile flags, named once: tests/test_probe_quick.py
+# produces assembly with them to look at the code the library really runs
+DEVICE_FLAGS = ["--offload-arch=gfx950", "-O3"]
 
 
 def _stale(out: str, inputs) -> bool:
@@ -41,7 +44,7 @@ def _stale(out: str, inputs) -> bool:
 def build(force: bool = False) -> str:
     if force or _stale(OUT, ALL_SRCS + ALL_HEADERS):
         subprocess.run(
-            [HIPCC, "--offload-arch=gfx950", "-O3", "-fPIC", "-shared", *ALL_SRCS, "-o", OUT],
+            [HIPCC, *DEVICE_FLAGS, "-fPIC", "-shared", *ALL_SRCS, "-o", OUT],
             check=True,
         )
     build_agent(force=force)

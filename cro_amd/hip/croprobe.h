@@ -25,8 +25,37 @@ struct CroProbeResult {
   char msg[256];
 };
 
-int cro_probe_run(int device, struct CroProbeResult* out);
+// nodeops/probe.py mirrors CroProbeResult and CroProbeOpts with ctypes
+// (tests/test_probe_quick.py compares sizeof/offsetof).
+struct CroProbeOpts {
+  double hbm_floor_gbps;     // 0 → 500
+  double bf16_floor_tflops;  // 0 → 100
+  // Self-test, for tests only.  Mode 1: the host flips bit selftest_bit of
+  // element selftest_elem (row * 16 + col, below 256) of the EXPECTED f32 tile
+  // before the compare, so the exact gate fires through data alone.
+  int selftest_mode;
+  int selftest_bit;
+  unsigned int selftest_elem;
+  int reserved;
+};
+
+// rc 0 ok, -1 HIP error or bad argument, then in this order: -2 f32 MFMA
+// mismatch, -3 HBM bandwidth below its floor, -4 bf16 rate below its floor.
+int cro_probe_run(int device, struct CroProbeResult* out);  // = run_opts(device, NULL, out)
+int cro_probe_run_opts(int device, const struct CroProbeOpts* opts, struct CroProbeResult* out);
+// Raw entries for tests, one per kernel of the quick probe (probe.hip).
+// -10 = bad argument.  K a multiple of 4, at most 4096.
 int cro_probe_mfma_f32(int device, const float* A, const float* B, float* D, int K);
+// bw_copy_kernel over n4 16-byte vectors with grid_blocks x 256 threads;
+// *guard_ok = the 64 vectors after dst untouched; -11 = src was changed.
+int cro_probe_copy(int device, const void* src_host, unsigned long long n4, int grid_blocks,
+                   void* dst_host, int* guard_ok);
+// The probe's own copy launch on its cached buffers, dst zeroed first: the
+// bytes of dst that are not 0x5a afterwards.
+int cro_probe_bw_selfcheck(int device, unsigned long long* n_bad,
+                           unsigned long long* first_bad);
+// mfma_bf16_rate_kernel; out_host gets blocks floats, or blocks * 256 with all_lanes.
+int cro_probe_bf16_sink(int device, int blocks, int iters, int all_lanes, float* out_host);
 void* cro_probe_alloc(int device, long long bytes);
 void cro_probe_free(void* p);
 int cro_probe_device_count(void);

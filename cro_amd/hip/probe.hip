@@ -22,13 +22,18 @@
 // Built standalone with hipcc for gfx950 only (no torch dependency):
 //   hipcc --offload-arch=gfx950 -O3 -fPIC -shared probe.hip -o libcroprobe.so
 //
-// C ABI consumed by cro_amd/nodeops/probe.py via ctypes.
+// C ABI consumed by cro_amd/nodeops/probe.py via ctypes.  Besides the probe
+// itself it has one raw entry per kernel (caller data in, raw output back)
+// and a self-check of the probe's own copy launch, for the exact tests in
+// tests/test_probe_quick_gpu.py.
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include <chrono>
 #include <cstdio>
 #include <cstring>
+#include <mutex>
+#include <vector>
 
 static double now_ms() {
   return std::chrono::duration<double, std::milli>(
@@ -92,6 +97,12 @@ __global__ void bw_copy_kernel(const float4* __restrict__ src,
 //    32-cycle/SIMD issue pipe of v_mfma_f32_32x32x16_bf16 saturated)
 // ---------------------------------------------------------------------------
 
+// kAllLanes = false is the probe's kernel: thread 0 of each block stores its
+// sum.  true stores every thread's sum (cro_probe_bf16_sink, for tests): the
+// operands have the closed form A[row][k] = 0.5 + 0.0625 * ((row + k) & 7),
+// B[k][col] = 0.25 + 0.03125 * ((3 * col + k) & 7) in every wave, so each
+// lane's sum is known exactly.
+template <bool kAllLanes>
 __global__ void mfma_bf16_rate_kernel(float* __restrict__ out, int iters) {
   bf16x8 a, b;
   // non-zero, non-uniform operands: zero inputs let DVFS overclock and
@@ -109,7 +120,11 @@ __global__ void mfma_bf16_rate_kernel(float* __restrict__ out, int iters) {
   }
   float s = 0.f;
   for (int i = 0; i < 16; ++i) s += acc0[i] + acc1[i] + acc2[i] + acc3[i];
-  if (threadIdx.x == 0) out[blockIdx.x] = s;
+  if constexpr (kAllLanes) {
+    out[blockIdx.x * 256 + threadIdx.x] = s;
+  } else {
+    if (threadIdx.x == 0) out[blockIdx.x] = s;
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -129,8 +144,11 @@ static void host_mfma_ref(const float* A, const float* B, float* D, int K) {
 
 // Per-device cached probe context: the probe runs on every attach, so
 // allocations and events are created once and reused — only the kernels,
-// copies and compares run per call.
+// copies and compares run per call.  The mutex serialises concurrent
+// reconcile workers on one device: without it two first calls both allocate,
+// and any two calls share e0/e1.
 struct ProbeCtx {
+  std::mutex mu;
   int ready = 0;
   long long vram_total = 0, vram_free = 0;  // hipMemGetInfo is sysfs-backed
                                             // and ms-scale: snapshot at init
@@ -143,10 +161,78 @@ struct ProbeCtx {
 };
 static ProbeCtx g_ctx[64];
 
-extern "C" int cro_probe_run(int device, struct CroProbeResult* out) {
+constexpr int kCheckK = 64;  // K of the probe's exact f32 check
+constexpr int kBlock = 256;
+constexpr int kBwGrid = 8192;
+constexpr size_t kBwBytes = (size_t)256 << 20;  // each of src and dst
+constexpr int kMaxTileK = 4096;
+constexpr int kGuardVecs = 64;  // cro_probe_copy: vectors after dst, preset to 0xA5
+constexpr unsigned long long kMaxCopyVecs = kBwBytes / sizeof(float4);
+constexpr int kMaxCopyGrid = 1 << 16;
+constexpr int kMaxSinkBlocks = 1024;
+constexpr int kMaxSinkIters = 1 << 16;
+
+static void launch_copy(const float4* src, float4* dst, size_t n4, int grid_blocks) {
+  hipLaunchKernelGGL(bw_copy_kernel, dim3(grid_blocks), dim3(kBlock), 0, 0, src, dst, n4);
+}
+
+// The probe's own copy: the launch whose bytes hbm_gbps is credited for.
+static void launch_probe_copy(const ProbeCtx* ctx) {
+  launch_copy(ctx->src, ctx->dst, kBwBytes / sizeof(float4), kBwGrid);
+}
+
+// Caller holds ctx->mu and has made `device` current.
+static int ensure_ctx(ProbeCtx* ctx, int device, struct CroProbeResult* out) {
+  if (ctx->ready) return 0;
+  CHECK(hipMalloc(&ctx->dA, 16 * kCheckK * sizeof(float)));
+  CHECK(hipMalloc(&ctx->dB, kCheckK * 16 * sizeof(float)));
+  CHECK(hipMalloc(&ctx->dD, 256 * sizeof(float)));
+  CHECK(hipMalloc(&ctx->src, kBwBytes));
+  CHECK(hipMalloc(&ctx->dst, kBwBytes));
+  CHECK(hipMemset(ctx->src, 0x5a, kBwBytes));
+  CHECK(hipMalloc(&ctx->sink, 1024 * sizeof(float)));
+  CHECK(hipEventCreate(&ctx->e0));
+  CHECK(hipEventCreate(&ctx->e1));
+  hipDeviceProp_t prop;
+  CHECK(hipGetDeviceProperties(&prop, device));
+  snprintf(ctx->gcn_arch, sizeof(ctx->gcn_arch), "%s", prop.gcnArchName);
+  size_t free_b = 0, total_b = 0;
+  CHECK(hipMemGetInfo(&free_b, &total_b));
+  ctx->vram_total = (long long)total_b;
+  ctx->vram_free = (long long)free_b;
+  // one warm round at init covers kernel-code upload; per-call warms are
+  // off the attach path
+  launch_probe_copy(ctx);
+  hipLaunchKernelGGL(mfma_bf16_rate_kernel<false>, dim3(1024), dim3(256), 0, 0, ctx->sink,
+                     64);
+  CHECK(hipDeviceSynchronize());
+  ctx->ready = 1;
+  return 0;
+}
+
+static int bad_opt(struct CroProbeResult* out, const char* what) {
+  snprintf(out->msg, sizeof(out->msg), "bad argument: %s", what);
+  out->ok = 0;
+  return -1;
+}
+
+extern "C" int cro_probe_run_opts(int device, const struct CroProbeOpts* opts,
+                                  struct CroProbeResult* out) {
   memset(out, 0, sizeof(*out));
   out->ok = 0;
   double t0 = now_ms();
+
+  struct CroProbeOpts o;
+  memset(&o, 0, sizeof(o));
+  if (opts) o = *opts;
+  // !(x >= 0) also refuses a NaN
+  if (!(o.hbm_floor_gbps >= 0.0)) return bad_opt(out, "hbm_floor_gbps");
+  if (!(o.bf16_floor_tflops >= 0.0)) return bad_opt(out, "bf16_floor_tflops");
+  if (o.selftest_mode < 0 || o.selftest_mode > 1) return bad_opt(out, "selftest_mode");
+  if (o.selftest_bit < 0 || o.selftest_bit > 31) return bad_opt(out, "selftest_bit");
+  if (o.selftest_elem >= 256) return bad_opt(out, "selftest_elem");
+  const double hbm_floor = o.hbm_floor_gbps > 0.0 ? o.hbm_floor_gbps : 500.0;
+  const double bf16_floor = o.bf16_floor_tflops > 0.0 ? o.bf16_floor_tflops : 100.0;
 
   int count = 0;
   CHECK(hipGetDeviceCount(&count));
@@ -155,12 +241,18 @@ extern "C" int cro_probe_run(int device, struct CroProbeResult* out) {
              device, count);
     return -1;
   }
+  ProbeCtx* ctx = (device < 64) ? &g_ctx[device] : nullptr;
+  if (ctx == nullptr) {
+    snprintf(out->msg, sizeof(out->msg), "device ordinal %d above cache limit", device);
+    return -1;
+  }
+  std::lock_guard<std::mutex> lock(ctx->mu);
   CHECK(hipSetDevice(device));
 
   // -- exact f32 MFMA ------------------------------------------------------
   out->t_setup_ms = now_ms() - t0;
   t0 = now_ms();
-  const int K = 64;
+  const int K = kCheckK;
   float hA[16 * K], hB[K * 16], hD[256], refD[256];
   unsigned s = 0x9e3779b9u;
   for (int i = 0; i < 16 * K; ++i) {
@@ -171,37 +263,8 @@ extern "C" int cro_probe_run(int device, struct CroProbeResult* out) {
     s = s * 1664525u + 1013904223u;
     hB[i] = ((float)(s >> 8) / 16777216.0f) - 0.5f;
   }
-  ProbeCtx* ctx = (device < 64) ? &g_ctx[device] : nullptr;
-  if (ctx == nullptr) {
-    snprintf(out->msg, sizeof(out->msg), "device ordinal %d above cache limit", device);
-    return -1;
-  }
-  const size_t bytes = (size_t)256 << 20;  // bw buffers (see below)
-  if (!ctx->ready) {
-    CHECK(hipMalloc(&ctx->dA, sizeof(hA)));
-    CHECK(hipMalloc(&ctx->dB, sizeof(hB)));
-    CHECK(hipMalloc(&ctx->dD, sizeof(hD)));
-    CHECK(hipMalloc(&ctx->src, bytes));
-    CHECK(hipMalloc(&ctx->dst, bytes));
-    CHECK(hipMemset(ctx->src, 0x5a, bytes));
-    CHECK(hipMalloc(&ctx->sink, 1024 * sizeof(float)));
-    CHECK(hipEventCreate(&ctx->e0));
-    CHECK(hipEventCreate(&ctx->e1));
-    hipDeviceProp_t prop;
-    CHECK(hipGetDeviceProperties(&prop, device));
-    snprintf(ctx->gcn_arch, sizeof(ctx->gcn_arch), "%s", prop.gcnArchName);
-    size_t free_b = 0, total_b = 0;
-    CHECK(hipMemGetInfo(&free_b, &total_b));
-    ctx->vram_total = (long long)total_b;
-    ctx->vram_free = (long long)free_b;
-    // one warm round at init covers kernel-code upload; per-call warms are
-    // off the attach path
-    hipLaunchKernelGGL(bw_copy_kernel, dim3(8192), dim3(256), 0, 0, ctx->src, ctx->dst,
-                       bytes / sizeof(float4));
-    hipLaunchKernelGGL(mfma_bf16_rate_kernel, dim3(1024), dim3(256), 0, 0, ctx->sink, 64);
-    CHECK(hipDeviceSynchronize());
-    ctx->ready = 1;
-  }
+  const size_t bytes = kBwBytes;  // bw buffers (see below)
+  if (ensure_ctx(ctx, device, out) != 0) return -1;
   snprintf(out->gcn_arch, sizeof(out->gcn_arch), "%s", ctx->gcn_arch);
   out->vram_total = ctx->vram_total;
   out->vram_free = ctx->vram_free;
@@ -211,6 +274,14 @@ extern "C" int cro_probe_run(int device, struct CroProbeResult* out) {
   CHECK(hipGetLastError());
   CHECK(hipMemcpy(hD, ctx->dD, sizeof(hD), hipMemcpyDeviceToHost));
   host_mfma_ref(hA, hB, refD, K);
+  if (o.selftest_mode == 1) {
+    // self-test, for tests only: one bit of one expected element is flipped,
+    // so the exact gate must fire on data alone (as coverage.hip's mode 1)
+    uint32_t u;
+    memcpy(&u, &refD[o.selftest_elem], sizeof(u));
+    u ^= 1u << o.selftest_bit;
+    memcpy(&refD[o.selftest_elem], &u, sizeof(u));
+  }
   out->mfma_f32_exact = (memcmp(hD, refD, sizeof(hD)) == 0) ? 1 : 0;
 
   out->t_mfma_ms = now_ms() - t0;
@@ -219,13 +290,10 @@ extern "C" int cro_probe_run(int device, struct CroProbeResult* out) {
   // 256 MiB src + dst from the cached context (2 GiB of traffic per
   // measurement — ample signal without putting hipMalloc on the
   // attach-latency path or pinning more of the 288 GB than a gate needs)
-  size_t n4 = bytes / sizeof(float4);
   hipEvent_t e0 = ctx->e0, e1 = ctx->e1;
-  dim3 grid(8192), block(256);
   CHECK(hipEventRecord(e0));
   const int reps = 8;
-  for (int i = 0; i < reps; ++i)
-    hipLaunchKernelGGL(bw_copy_kernel, grid, block, 0, 0, ctx->src, ctx->dst, n4);
+  for (int i = 0; i < reps; ++i) launch_probe_copy(ctx);
   CHECK(hipEventRecord(e1));
   CHECK(hipEventSynchronize(e1));
   float ms = 0.f;
@@ -237,7 +305,8 @@ extern "C" int cro_probe_run(int device, struct CroProbeResult* out) {
   // -- bf16 MFMA rate ------------------------------------------------------
   const int blocks = 1024, iters = 2048;
   CHECK(hipEventRecord(e0));
-  hipLaunchKernelGGL(mfma_bf16_rate_kernel, dim3(blocks), dim3(256), 0, 0, ctx->sink, iters);
+  hipLaunchKernelGGL(mfma_bf16_rate_kernel<false>, dim3(blocks), dim3(256), 0, 0, ctx->sink,
+                     iters);
   CHECK(hipEventRecord(e1));
   CHECK(hipEventSynchronize(e1));
   CHECK(hipEventElapsedTime(&ms, e0, e1));
@@ -252,11 +321,11 @@ extern "C" int cro_probe_run(int device, struct CroProbeResult* out) {
     snprintf(out->msg, sizeof(out->msg), "f32 MFMA mismatch vs host fmaf chain");
     return -2;
   }
-  if (out->hbm_gbps < 500.0) {
+  if (out->hbm_gbps < hbm_floor) {
     snprintf(out->msg, sizeof(out->msg), "HBM bandwidth %.0f GB/s below floor", out->hbm_gbps);
     return -3;
   }
-  if (out->bf16_tflops < 100.0) {
+  if (out->bf16_tflops < bf16_floor) {
     snprintf(out->msg, sizeof(out->msg), "bf16 MFMA %.0f TF below floor", out->bf16_tflops);
     return -4;
   }
@@ -265,27 +334,145 @@ extern "C" int cro_probe_run(int device, struct CroProbeResult* out) {
   return 0;
 }
 
+extern "C" int cro_probe_run(int device, struct CroProbeResult* out) {
+  return cro_probe_run_opts(device, nullptr, out);
+}
+
+// ---------------------------------------------------------------------------
+// raw entries for tests: each kernel of the probe on caller data
+// ---------------------------------------------------------------------------
+
 // Raw MFMA tile entry for numerics tests: D(16x16) = A(16xK) @ B(Kx16) on
-// the f32 matrix pipe; compared against a PyTorch fp32 reference in
-// tests/test_gpu.py.  K must be a multiple of 4.
+// the f32 matrix pipe; compared bit for bit against the k-ordered fmaf chain
+// in tests/test_probe_quick_gpu.py.  K a multiple of 4, at most 4096.
 extern "C" int cro_probe_mfma_f32(int device, const float* A, const float* B,
                                   float* D, int K) {
+  if (A == nullptr || B == nullptr || D == nullptr) return -10;
+  if (K <= 0 || K > kMaxTileK || (K & 3) != 0) return -10;
+  const size_t in_bytes = (size_t)16 * K * sizeof(float), out_bytes = 256 * sizeof(float);
+  if (hipSetDevice(device) != hipSuccess) return -1;
+  float *dA = nullptr, *dB = nullptr, *dD = nullptr;
+  hipError_t e = hipMalloc(&dA, in_bytes);
+  if (e == hipSuccess) e = hipMalloc(&dB, in_bytes);
+  if (e == hipSuccess) e = hipMalloc(&dD, out_bytes);
+  if (e == hipSuccess) e = hipMemcpy(dA, A, in_bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dB, B, in_bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(mfma_f32_check_kernel, dim3(1), dim3(64), 0, 0, dA, dB, dD, K);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(D, dD, out_bytes, hipMemcpyDeviceToHost);
+  if (dA) (void)hipFree(dA);
+  if (dB) (void)hipFree(dB);
+  if (dD) (void)hipFree(dD);
+  return e == hipSuccess ? 0 : -1;
+}
+
+// bw_copy_kernel on caller data: n4 16-byte vectors, grid_blocks x 256
+// threads.  dst is followed by 64 guard vectors preset to 0xA5 (as the whole
+// of dst is, so a vector the kernel skipped shows); *guard_ok tells whether
+// they came back untouched.  Returns 0, -10 for a bad argument, -1 for a HIP
+// error and -11 when the kernel changed src.
+extern "C" int cro_probe_copy(int device, const void* src_host, unsigned long long n4,
+                              int grid_blocks, void* dst_host, int* guard_ok) {
+  if (src_host == nullptr || dst_host == nullptr || guard_ok == nullptr) return -10;
+  if (n4 == 0 || n4 > kMaxCopyVecs) return -10;
+  if (grid_blocks < 1 || grid_blocks > kMaxCopyGrid) return -10;
+  *guard_ok = 0;
+  const size_t bytes = (size_t)n4 * sizeof(float4);
+  const size_t guard_bytes = kGuardVecs * sizeof(float4);
+  if (hipSetDevice(device) != hipSuccess) return -1;
+  float4 *src = nullptr, *dst = nullptr;
+  std::vector<unsigned char> back(bytes > guard_bytes ? bytes : guard_bytes);
+  hipError_t e = hipMalloc(&src, bytes);
+  if (e == hipSuccess) e = hipMalloc(&dst, bytes + guard_bytes);
+  if (e == hipSuccess) e = hipMemcpy(src, src_host, bytes, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(dst, 0xA5, bytes + guard_bytes);
+  if (e == hipSuccess) {
+    launch_copy(src, dst, (size_t)n4, grid_blocks);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(dst_host, dst, bytes, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(back.data(), dst + n4, guard_bytes, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) {
+    int ok = 1;
+    for (size_t i = 0; i < guard_bytes; ++i) ok &= back[i] == 0xA5;
+    *guard_ok = ok;
+    e = hipMemcpy(back.data(), src, bytes, hipMemcpyDeviceToHost);
+  }
+  const bool src_same = e == hipSuccess && memcmp(back.data(), src_host, bytes) == 0;
+  if (src) (void)hipFree(src);
+  if (dst) (void)hipFree(dst);
+  if (e != hipSuccess) return -1;
+  return src_same ? 0 : -11;
+}
+
+// The probe's own copy launch, once, on the cached context with dst zeroed
+// first: *n_bad counts the bytes of dst that are not src's 0x5a afterwards,
+// *first_bad is the lowest such byte offset (~0 when none).  Shows that the
+// grid and size hbm_gbps is credited for write every byte of dst.
+extern "C" int cro_probe_bw_selfcheck(int device, unsigned long long* n_bad,
+                                      unsigned long long* first_bad) {
+  if (n_bad == nullptr || first_bad == nullptr) return -10;
+  *n_bad = 0;
+  *first_bad = ~0ull;
   struct CroProbeResult scratch;
   struct CroProbeResult* out = &scratch;  // reuse CHECK() plumbing
   memset(out, 0, sizeof(*out));
-  if (K <= 0 || (K & 3) != 0) return -10;
+  int count = 0;
+  CHECK(hipGetDeviceCount(&count));
+  if (device < 0 || device >= count || device >= 64) return -1;
+  ProbeCtx* ctx = &g_ctx[device];
+  std::lock_guard<std::mutex> lock(ctx->mu);
   CHECK(hipSetDevice(device));
-  float *dA, *dB, *dD;
-  CHECK(hipMalloc(&dA, 16 * K * sizeof(float)));
-  CHECK(hipMalloc(&dB, K * 16 * sizeof(float)));
-  CHECK(hipMalloc(&dD, 256 * sizeof(float)));
-  CHECK(hipMemcpy(dA, A, 16 * K * sizeof(float), hipMemcpyHostToDevice));
-  CHECK(hipMemcpy(dB, B, K * 16 * sizeof(float), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(mfma_f32_check_kernel, dim3(1), dim3(64), 0, 0, dA, dB, dD, K);
+  if (ensure_ctx(ctx, device, out) != 0) return -1;
+  CHECK(hipMemset(ctx->dst, 0, kBwBytes));
+  launch_probe_copy(ctx);
   CHECK(hipGetLastError());
-  CHECK(hipMemcpy(D, dD, 256 * sizeof(float), hipMemcpyDeviceToHost));
-  (void)hipFree(dA); (void)hipFree(dB); (void)hipFree(dD);
+  CHECK(hipDeviceSynchronize());
+  const size_t chunk = (size_t)32 << 20;
+  std::vector<unsigned char> host(chunk);
+  for (size_t off = 0; off < kBwBytes; off += chunk) {
+    CHECK(hipMemcpy(host.data(), (const unsigned char*)ctx->dst + off, chunk,
+                    hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < chunk; i += 8) {
+      unsigned long long w;
+      memcpy(&w, &host[i], 8);
+      if (w == 0x5a5a5a5a5a5a5a5aull) continue;
+      for (size_t j = i; j < i + 8; ++j) {
+        if (host[j] == 0x5a) continue;
+        if (*n_bad == 0) *first_bad = off + j;
+        ++*n_bad;
+      }
+    }
+  }
   return 0;
+}
+
+// mfma_bf16_rate_kernel on `blocks` x 256 threads for `iters` iterations.
+// all_lanes = 0: the probe's kernel, out_host gets `blocks` floats (thread 0
+// of each block); else every thread's sum, blocks * 256 floats.  The device
+// buffer is preset to 0xFF, so a value the kernel did not store reads as NaN.
+extern "C" int cro_probe_bf16_sink(int device, int blocks, int iters, int all_lanes,
+                                   float* out_host) {
+  if (out_host == nullptr) return -10;
+  if (blocks < 1 || blocks > kMaxSinkBlocks) return -10;
+  if (iters < 0 || iters > kMaxSinkIters) return -10;
+  const size_t bytes = (size_t)blocks * (all_lanes ? kBlock : 1) * sizeof(float);
+  if (hipSetDevice(device) != hipSuccess) return -1;
+  float* d = nullptr;
+  hipError_t e = hipMalloc(&d, bytes);
+  if (e == hipSuccess) e = hipMemset(d, 0xFF, bytes);
+  if (e == hipSuccess) {
+    if (all_lanes)
+      hipLaunchKernelGGL(mfma_bf16_rate_kernel<true>, dim3(blocks), dim3(kBlock), 0, 0, d, iters);
+    else
+      hipLaunchKernelGGL(mfma_bf16_rate_kernel<false>, dim3(blocks), dim3(kBlock), 0, 0, d, iters);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpy(out_host, d, bytes, hipMemcpyDeviceToHost);
+  if (d) (void)hipFree(d);
+  return e == hipSuccess ? 0 : -1;
 }
 
 // Raw VRAM alloc/free for the self-identification fingerprint

@@ -31,6 +31,19 @@ class CroProbeResult(ctypes.Structure):
     ]
 
 
+class CroProbeOpts(ctypes.Structure):
+    """Mirror of ``struct CroProbeOpts`` (cro_amd/hip/croprobe.h)."""
+
+    _fields_ = [
+        ("hbm_floor_gbps", ctypes.c_double),
+        ("bf16_floor_tflops", ctypes.c_double),
+        ("selftest_mode", ctypes.c_int),
+        ("selftest_bit", ctypes.c_int),
+        ("selftest_elem", ctypes.c_uint),
+        ("reserved", ctypes.c_int),
+    ]
+
+
 class CroIntegrityOpts(ctypes.Structure):
     """Mirror of ``struct CroIntegrityOpts`` (cro_amd/hip/croprobe.h)."""
 
@@ -183,6 +196,26 @@ def load_library(required: Optional[bool] = None) -> Optional[ctypes.CDLL]:
     lib = ctypes.CDLL(path)
     lib.cro_probe_run.argtypes = [ctypes.c_int, ctypes.POINTER(CroProbeResult)]
     lib.cro_probe_run.restype = ctypes.c_int
+    lib.cro_probe_run_opts.argtypes = [
+        ctypes.c_int, ctypes.POINTER(CroProbeOpts), ctypes.POINTER(CroProbeResult),
+    ]
+    lib.cro_probe_run_opts.restype = ctypes.c_int
+    f32p = ctypes.POINTER(ctypes.c_float)
+    lib.cro_probe_mfma_f32.argtypes = [ctypes.c_int, f32p, f32p, f32p, ctypes.c_int]
+    lib.cro_probe_mfma_f32.restype = ctypes.c_int
+    lib.cro_probe_copy.argtypes = [
+        ctypes.c_int, ctypes.c_void_p, ctypes.c_ulonglong, ctypes.c_int, ctypes.c_void_p,
+        ctypes.POINTER(ctypes.c_int),
+    ]
+    lib.cro_probe_copy.restype = ctypes.c_int
+    lib.cro_probe_bw_selfcheck.argtypes = [
+        ctypes.c_int, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong),
+    ]
+    lib.cro_probe_bw_selfcheck.restype = ctypes.c_int
+    lib.cro_probe_bf16_sink.argtypes = [
+        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+    ]
+    lib.cro_probe_bf16_sink.restype = ctypes.c_int
     lib.cro_probe_device_count.restype = ctypes.c_int
     lib.cro_probe_pci_bus_id.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
     lib.cro_probe_pci_bus_id.restype = ctypes.c_int
@@ -266,10 +299,26 @@ def hip_device_for_bdf(pci_bdf: str) -> Optional[int]:
     return None
 
 
-def run_probe(device: int = 0) -> dict:
+def _probe_opts(hbm_floor_gbps=0.0, bf16_floor_tflops=0.0, selftest_mode=0, selftest_bit=0,
+                selftest_elem=0) -> "CroProbeOpts":
+    return CroProbeOpts(
+        hbm_floor_gbps=float(hbm_floor_gbps), bf16_floor_tflops=float(bf16_floor_tflops),
+        selftest_mode=int(selftest_mode), selftest_bit=int(selftest_bit),
+        selftest_elem=int(selftest_elem) & 0xFFFFFFFF,
+    )
+
+
+def run_probe(device: int = 0, **opts) -> dict:
+    """Quick probe.  Options as ``struct CroProbeOpts``; zero takes the library
+    default (floors of 500 GB/s and 100 TF).  The ``selftest_*`` options are
+    for tests.  Without options this is ``cro_probe_run``, as ever."""
     lib = load_library(required=True)
     res = CroProbeResult()
-    rc = lib.cro_probe_run(device, ctypes.byref(res))
+    if opts:
+        c_opts = _probe_opts(**opts)
+        rc = lib.cro_probe_run_opts(device, ctypes.byref(c_opts), ctypes.byref(res))
+    else:
+        rc = lib.cro_probe_run(device, ctypes.byref(res))
     return {
         "ok": bool(res.ok) and rc == 0,
         "rc": rc,
@@ -293,6 +342,136 @@ def probe_fn_for_nodeops(gpu) -> dict:
     if dev is None:
         dev = 0
     return run_probe(dev)
+
+
+# -- quick probe: raw kernel entries and their references, for tests ---------------
+
+
+def mfma_f32_tile(device: int, a, b):
+    """One wave of the quick probe's f32 check kernel on caller data:
+    16xK @ Kx16 → float32 16x16, K a multiple of 4, at most 4096."""
+    import numpy as np
+
+    lib = load_library(required=True)
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    b = np.ascontiguousarray(b, dtype=np.float32)
+    k = a.shape[1] if a.ndim == 2 else -1
+    if a.shape != (16, k) or b.shape != (k, 16):
+        raise ValueError("f32 tile wants A 16xK and B Kx16")
+    d = np.zeros((16, 16), dtype=np.float32)
+    f32p = ctypes.POINTER(ctypes.c_float)
+    rc = lib.cro_probe_mfma_f32(device, a.ctypes.data_as(f32p), b.ctypes.data_as(f32p),
+                                d.ctypes.data_as(f32p), k)
+    if rc != 0:
+        raise RuntimeError(f"cro_probe_mfma_f32 failed: rc={rc}")
+    return d
+
+
+def copy_vectors(device: int, words, grid_blocks: int) -> dict:
+    """Run the quick probe's copy kernel over ``words`` (uint32, four per
+    16-byte vector) with ``grid_blocks`` x 256 threads.  Returns the copy, and
+    whether the 64 guard vectors after it and the source came back untouched."""
+    import numpy as np
+
+    lib = load_library(required=True)
+    src = np.ascontiguousarray(words, dtype=np.uint32)
+    if src.ndim != 1 or src.size % 4:
+        raise ValueError("copy_vectors wants a flat array of whole 16-byte vectors")
+    dst = np.zeros_like(src)
+    guard_ok = ctypes.c_int(0)
+    rc = lib.cro_probe_copy(device, src.ctypes.data, src.size // 4, int(grid_blocks),
+                            dst.ctypes.data, ctypes.byref(guard_ok))
+    if rc not in (0, -11):
+        raise RuntimeError(f"cro_probe_copy failed: rc={rc}")
+    return {"dst": dst, "guard_ok": bool(guard_ok.value), "src_unchanged": rc == 0}
+
+
+def bw_selfcheck(device: int = 0) -> dict:
+    """The quick probe's own copy launch, once, into a zeroed ``dst``: how many
+    of the bytes it is credited for did not arrive."""
+    lib = load_library(required=True)
+    n_bad = ctypes.c_ulonglong()
+    first_bad = ctypes.c_ulonglong()
+    rc = lib.cro_probe_bw_selfcheck(device, ctypes.byref(n_bad), ctypes.byref(first_bad))
+    if rc != 0:
+        raise RuntimeError(f"cro_probe_bw_selfcheck failed: rc={rc}")
+    return {"n_bad": n_bad.value, "first_bad": first_bad.value}
+
+
+def bf16_sink(device: int, blocks: int, iters: int, all_lanes: bool):
+    """What the quick probe's bf16 rate kernel stores: thread 0's sum of each
+    block, or with ``all_lanes`` every thread's (blocks * 256 values)."""
+    import numpy as np
+
+    lib = load_library(required=True)
+    n = max(int(blocks), 0) * (256 if all_lanes else 1)
+    out = np.zeros(n, dtype=np.float32)
+    rc = lib.cro_probe_bf16_sink(device, int(blocks), int(iters), 1 if all_lanes else 0,
+                                 out.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"cro_probe_bf16_sink failed: rc={rc}")
+    return out
+
+
+def fmaf_chain(a, b):
+    """The k-ordered float32 fused-multiply-add chain of ``a`` (MxK) @ ``b``
+    (KxN), which the f32 matrix pipe of gfx950 equals bit for bit, and the
+    number of steps at which this numpy form could differ from a true ``fmaf``.
+
+    The product of two float32 is exact in float64; the sum with the
+    accumulator is rounded once to float64 and then to float32.  That double
+    rounding differs from the single one of ``fmaf`` only when the float64 sum
+    lies exactly half way between two neighbouring float32 values — for a
+    normal result: the low 29 bits of the float64 word are ``1 << 28``.  Such
+    steps are counted (for subnormal results too, where the float32 grid is
+    coarser); at a count of 0 the result is the true chain."""
+    import numpy as np
+
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    b = np.ascontiguousarray(b, dtype=np.float32)
+    if a.ndim != 2 or b.ndim != 2 or a.shape[1] != b.shape[0]:
+        raise ValueError("fmaf_chain wants A MxK and B KxN")
+    acc = np.zeros((a.shape[0], b.shape[1]), dtype=np.float32)
+    ties = 0
+    for k in range(a.shape[1]):
+        prod = a[:, k : k + 1].astype(np.float64) * b[k : k + 1, :].astype(np.float64)
+        total = prod + acc.astype(np.float64)
+        acc = total.astype(np.float32)
+        # both differences are exact: a tie is half the way to the neighbour
+        # of the rounded value on the side of the float64 sum
+        off = total - acc.astype(np.float64)
+        toward = np.where(off > 0, np.float32(np.inf), np.float32(-np.inf))
+        gap = np.nextafter(acc, toward).astype(np.float64) - acc.astype(np.float64)
+        with np.errstate(invalid="ignore"):
+            ties += int(np.count_nonzero((off != 0) & (2.0 * off == gap)))
+    return acc, ties
+
+
+def quick_bf16_tile():
+    """Closed form of the quick probe's bf16 rate kernel: the operands every
+    wave holds, A 32x16 and B 16x32, and D = A @ B (float64, exact)."""
+    import numpy as np
+
+    row, k = np.meshgrid(np.arange(32), np.arange(16), indexing="ij")
+    a = 0.5 + 0.0625 * ((row + k) & 7)
+    kk, col = np.meshgrid(np.arange(16), np.arange(32), indexing="ij")
+    b = 0.25 + 0.03125 * ((3 * col + kk) & 7)
+    return a, b, a @ b
+
+
+def quick_bf16_lane_rows(lane: int):
+    """Rows of the 32x32 tile that lane ``lane`` of a wave accumulates (of
+    column ``lane & 31``): register r is row (r & 3) + 8 (r >> 2) + 4 (lane >> 5)."""
+    return [(r & 3) + 8 * (r >> 2) + 4 * (lane >> 5) for r in range(16)]
+
+
+def quick_bf16_lane_sums(iters: int):
+    """What each of a wave's 64 lanes sums up in the rate kernel after ``iters``
+    iterations of its four accumulators (float64)."""
+    import numpy as np
+
+    d = quick_bf16_tile()[2]
+    return np.array([4.0 * iters * d[quick_bf16_lane_rows(l), l & 31].sum() for l in range(64)])
 
 
 def run_integrity(
@@ -526,18 +705,13 @@ def compute_inputs(seed: int = 0) -> dict:
 
 def compute_expected_tiles(seed: int = 0) -> dict:
     """numpy mirror of the three expected tiles.  f32 is the k-ordered fmaf
-    chain: the product of two float32 is exact in float64 and the sum is
-    rounded once to float64 before the rounding to float32, which differs
-    from a true fused multiply-add only when the float64 sum lands exactly on
-    a float32 tie — the CPU test compares this tile with the header's."""
+    chain (``fmaf_chain``) — the CPU test compares this tile with the
+    header's."""
     import numpy as np
 
     inputs = compute_inputs(seed)
     a32, b32 = inputs["f32"]
-    acc = np.zeros((16, 16), dtype=np.float32)
-    for k in range(a32.shape[1]):
-        prod = a32[:, k : k + 1].astype(np.float64) * b32[k : k + 1, :].astype(np.float64)
-        acc = (prod + acc.astype(np.float64)).astype(np.float32)
+    acc, _ = fmaf_chain(a32, b32)
     a8, b8 = inputs["i8"]
     a16, b16 = inputs["bf16"]
     return {
