@@ -319,9 +319,9 @@ void print_compute(const CroComputeResult& r) {
          r.t_total_ms, r.failed_test, r.msg);
 }
 
-// --compute and/or --deep: the quick probe first, then the compute-coverage
-// stage, then the data-integrity stage; a device that failed a stage is not
-// stressed further.  Top-level "ok" and "msg" then cover all stages run.
+// The quick probe first, then with --compute the compute-coverage stage, then
+// with --deep the data-integrity stage; a device that failed a stage is not
+// stressed further.  Top-level "ok" and "msg" cover all stages run.
 int cmd_probe_staged(int device, bool compute, const CroComputeOpts& copts, bool deep,
                      const CroIntegrityOpts& opts) {
   CroProbeResult result;
@@ -363,18 +363,6 @@ int cmd_probe_staged(int device, bool compute, const CroComputeOpts& copts, bool
   }
   printf("}\n");
   return ok ? 0 : 1;
-}
-
-int cmd_probe(int device) {
-  CroProbeResult result;
-  int rc = cro_probe_run(device, &result);
-  printf("{\"ok\":%s,\"rc\":%d,\"mfma_f32_exact\":%s,\"hbm_gbps\":%.1f,"
-         "\"bf16_tflops\":%.1f,\"vram_total\":%lld,\"vram_free\":%lld,"
-         "\"gcn_arch\":\"%s\",\"msg\":\"%s\"}\n",
-         result.ok ? "true" : "false", rc, result.mfma_f32_exact ? "true" : "false",
-         result.hbm_gbps, result.bf16_tflops, result.vram_total, result.vram_free,
-         result.gcn_arch, result.msg);
-  return result.ok ? 0 : 1;
 }
 
 }  // namespace
@@ -419,8 +407,7 @@ int main(int argc, char** argv) {
         return 1;
       }
     }
-    if (deep || compute) return cmd_probe_staged(device, compute, compute_opts, deep, integ_opts);
-    return cmd_probe(device);
+    return cmd_probe_staged(device, compute, compute_opts, deep, integ_opts);
   }
   if (cmd == "drain") return cmd_drain(bdf);
   if (cmd == "rescan") return cmd_rescan();

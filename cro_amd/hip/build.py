@@ -15,15 +15,19 @@ import sys
 HIP_DIR = os.path.dirname(os.path.abspath(__file__))
 AGENT_DIR = os.path.join(os.path.dirname(HIP_DIR), "agent")
 SRC = os.path.join(HIP_DIR, "probe.hip")
-# quick probe + deep (data-integrity) probe, one shared library
+# quick probe + deep (data-integrity) probe + compute-coverage stage, one
+# shared library: ALL_SRCS, rebuilt when any of ALL_HEADERS changes
 SRCS = [SRC, os.path.join(HIP_DIR, "integrity.hip")]
 HEADERS = [os.path.join(HIP_DIR, "croprobe.h"), os.path.join(HIP_DIR, "cropattern.h")]
 # compute-coverage stage: one more source and header of the same library
 # (listed apart: tests/test_probe_integrity.py pins what SRCS and HEADERS hold)
 COVERAGE_SRC = os.path.join(HIP_DIR, "coverage.hip")
 COVERAGE_HEADER = os.path.join(HIP_DIR, "crocoverage.h")
+# what the three sources share and nothing else includes: host plumbing and
+# the wave-level matrix code
+INTERNAL_HEADERS = [os.path.join(HIP_DIR, "crohost.h"), os.path.join(HIP_DIR, "cromfma.h")]
 ALL_SRCS = SRCS + [COVERAGE_SRC]
-ALL_HEADERS = HEADERS + [COVERAGE_HEADER]
+ALL_HEADERS = HEADERS + [COVERAGE_HEADER] + INTERNAL_HEADERS
 OUT = os.path.join(HIP_DIR, "libcroprobe.so")
 AGENT_SRC = os.path.join(AGENT_DIR, "croagent.cpp")
 AGENT_OUT = os.path.join(AGENT_DIR, "croagent")

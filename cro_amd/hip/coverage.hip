@@ -26,27 +26,21 @@
 // The location is for the report only; HIP promises nothing about placement,
 // so coverage gates only when the caller sets min_cu_fraction.
 //
-// Compiled with probe.hip and integrity.hip into libcroprobe.so.
+// Compiled with probe.hip and integrity.hip into libcroprobe.so; host plumbing
+// shared with them in crohost.h, one wave's matrix products and result maps
+// shared with probe.hip in cromfma.h.
 
 #include <hip/hip_runtime.h>
-#include <chrono>
-#include <cstdio>
 #include <cstring>
-#include <mutex>
 #include <vector>
 
+#include "crohost.h"
+#include "cromfma.h"
 #include "cropattern.h"
 #include "croprobe.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
-
-constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
 // ≈0.035 ms per repeat on an MI355X: 16 keeps the stage at the cost of one of
 // the quick probe's rate sections (profiles/compute_probe_mi355x.md)
@@ -55,84 +49,18 @@ constexpr int kDefaultRounds = 4;
 constexpr int kMaxRounds = 64;
 constexpr int kMaxGrid = 1 << 16;
 constexpr int kMaxIters = 1 << 16;
-constexpr int kMaxTileK = 4096;
 
-// ---------------------------------------------------------------------------
-// one wave's matrix products (shared by the coverage kernel and the raw tile
-// entry).  Operand lane maps, lane l of 64:
-//   f32 16x16x4   A[l&15][k = l>>4],             B[k = l>>4][l&15]
-//   i8  16x16x64  A[l&15][k = 16(l>>4) + j],     B[k = 16(l>>4) + j][l&15]
-//                 j = 0..15, byte j&3 of register j>>2 (derived from the
-//                 bf16 16x16x32 map; proved bit-exactly on the GPU by the
-//                 lane-map tests through cro_probe_mfma_tile)
-//   bf16 32x32x16 A[l&31][k = 8(l>>5) + j],      B[k = 8(l>>5) + j][l&31]
-// Result maps (dtype-independent): 16x16 register r is row 4(l>>4) + r,
-// column l&15; 32x32 register r is row (r&3) + 8(r>>2) + 4(l>>5), column l&31.
-// ---------------------------------------------------------------------------
-
-__device__ inline f32x4 wave_mfma_f32(const float* __restrict__ A,
-                                      const float* __restrict__ B, int K, uint32_t lane) {
-  const uint32_t rc = lane & 15, kh = lane >> 4;
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  for (int k0 = 0; k0 < K; k0 += 4) {
-    const float a = A[rc * K + (k0 + kh)];
-    const float b = B[(k0 + kh) * 16 + rc];
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);
-  }
-  return acc;
-}
-
-// A rows are 16-byte aligned: K is a multiple of 64 and the base comes from
-// hipMalloc.
-__device__ inline i32x4 wave_mfma_i8(const int8_t* __restrict__ A,
-                                     const int8_t* __restrict__ B, int K, uint32_t lane) {
-  const uint32_t rc = lane & 15, kh = lane >> 4;
-  i32x4 acc = {0, 0, 0, 0};
-  for (int k0 = 0; k0 < K; k0 += 64) {
-    const int kb = k0 + 16 * (int)kh;
-    const i32x4 a = *reinterpret_cast<const i32x4*>(A + rc * K + kb);
-    i32x4 b;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      uint32_t w = 0;
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        w |= (uint32_t)(uint8_t)B[(kb + 4 * q + j) * 16 + rc] << (8 * j);
-      b[q] = (int)w;
-    }
-    acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, acc, 0, 0, 0);
-  }
-  return acc;
-}
-
-__device__ inline f32x16 wave_mfma_bf16(const uint16_t* __restrict__ A,
-                                        const uint16_t* __restrict__ B, int K,
-                                        uint32_t lane) {
-  const uint32_t rc = lane & 31, h = lane >> 5;
-  f32x16 acc = {};
-  for (int k0 = 0; k0 < K; k0 += 16) {
-    const int kb = k0 + 8 * (int)h;
-    const u16x8 au = *reinterpret_cast<const u16x8*>(A + rc * K + kb);
-    u16x8 bu;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) bu[j] = B[(kb + j) * 32 + rc];
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, au),
-                                                  __builtin_bit_cast(bf16x8, bu), acc, 0, 0,
-                                                  0);
-  }
-  return acc;
-}
-
+// one wave of the coverage kernel's i8 or bf16 product (cromfma.h), stored
+// through the result maps: the raw tile entry's kernel
 __global__ __launch_bounds__(64) void mfma_tile_kernel(int kind, const void* A, const void* B,
                                                        void* D, int K) {
   const uint32_t lane = threadIdx.x;  // exactly one wave of 64
   if (kind == 1) {
     const i32x4 acc = wave_mfma_i8((const int8_t*)A, (const int8_t*)B, K, lane);
-    for (int r = 0; r < 4; ++r) ((int*)D)[((lane >> 4) * 4 + r) * 16 + (lane & 15)] = acc[r];
+    for (int r = 0; r < 4; ++r) ((int*)D)[mfma_elem16(lane, r)] = acc[r];
   } else {
     const f32x16 acc = wave_mfma_bf16((const uint16_t*)A, (const uint16_t*)B, K, lane);
-    for (int r = 0; r < 16; ++r)
-      ((float*)D)[((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * 32 + (lane & 31)] = acc[r];
+    for (int r = 0; r < 16; ++r) ((float*)D)[mfma_elem32(lane, r)] = acc[r];
   }
 }
 
@@ -189,15 +117,13 @@ struct Tally {
 
 __device__ inline uint32_t f32_bits(float x) { return __builtin_bit_cast(uint32_t, x); }
 
+// Expected content of LDS vector v.  A function of the 32-bit vector index on
+// purpose: with the widening written at the two call sites the compiler folds
+// the march's address arithmetic differently, and the kernel measured about
+// 1 % slower on an MI355X.
 __device__ inline uint4 lds_want(uint64_t base_word, uint32_t v, uint32_t seed,
                                  uint32_t invert) {
-  const uint64_t w = base_word + ((uint64_t)v << 2);
-  uint4 want;
-  want.x = cro_pattern_word(w + 0, seed, invert);
-  want.y = cro_pattern_word(w + 1, seed, invert);
-  want.z = cro_pattern_word(w + 2, seed, invert);
-  want.w = cro_pattern_word(w + 3, seed, invert);
-  return want;
+  return cro_pattern_vec4(base_word + ((uint64_t)v << 2), seed, invert);
 }
 
 __global__ __launch_bounds__(kBlock) void coverage_kernel(CovParams p) {
@@ -222,13 +148,13 @@ __global__ __launch_bounds__(kBlock) void coverage_kernel(CovParams p) {
   int want_i8[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    elem16[r] = ((lane >> 4) * 4 + r) * 16 + (lane & 15);
+    elem16[r] = mfma_elem16(lane, r);
     want_f32[r] = p.E32[elem16[r]];
     want_i8[r] = p.E8[elem16[r]];
   }
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    elem32[r] = ((r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * 32 + (lane & 31);
+    elem32[r] = mfma_elem32(lane, r);
     want_bf16[r] = p.E16[elem32[r]];
   }
 
@@ -320,23 +246,13 @@ __global__ __launch_bounds__(kBlock) void coverage_kernel(CovParams p) {
 // host side
 // ---------------------------------------------------------------------------
 
-double now_ms() {
-  return std::chrono::duration<double, std::milli>(
-             std::chrono::steady_clock::now().time_since_epoch())
-      .count();
-}
-
-// Per-device cached context (as ProbeCtx in probe.hip): inputs and expected
-// tiles are built and uploaded once per device (and again only when the seed
-// changes); the record buffer grows on demand.  The mutex serialises
-// concurrent reconcile workers on one device.
-struct CovCtx {
-  std::mutex mu;
-  int ready = 0;
+// Per-device cached context (CtxBase, crohost.h): inputs and expected tiles
+// are built and uploaded once per device (and again only when the seed
+// changes); the record buffer grows on demand.
+struct CovCtx : CtxBase {
   int tiles_ready = 0;
   uint32_t seed = 0;
   int cus = 0;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
   float *dA32 = nullptr, *dB32 = nullptr, *dE32 = nullptr;
   int8_t *dA8 = nullptr, *dB8 = nullptr;
   int* dE8 = nullptr;
@@ -349,26 +265,7 @@ struct CovCtx {
   CroCoverageRecord* d_records = nullptr;
   size_t records_cap = 0;
 };
-CovCtx g_cctx[64];
-
-#define CCHECK(expr)                                                         \
-  do {                                                                       \
-    hipError_t _e = (expr);                                                  \
-    if (_e != hipSuccess) {                                                  \
-      snprintf(out->msg, sizeof(out->msg), "%s failed: %s", #expr,           \
-               hipGetErrorString(_e));                                       \
-      out->ok = 0;                                                           \
-      out->rc = -1;                                                          \
-      return -1;                                                             \
-    }                                                                        \
-  } while (0)
-
-int bad_arg(CroComputeResult* out, const char* what) {
-  snprintf(out->msg, sizeof(out->msg), "bad argument: %s", what);
-  out->ok = 0;
-  out->rc = -1;
-  return -1;
-}
+CovCtx g_cctx[kMaxDevices];
 
 int upload_tiles(CovCtx* ctx, uint32_t seed, CroComputeResult* out) {
   static float A32[16 * CRO_COV_F32_K], B32[CRO_COV_F32_K * 16];
@@ -383,15 +280,15 @@ int upload_tiles(CovCtx* ctx, uint32_t seed, CroComputeResult* out) {
   cro_cov_ref_i8(A8, B8, ctx->hE8);
   cro_cov_make_bf16(seed, Ai, Bi, A16, B16);
   cro_cov_ref_bf16(Ai, Bi, ctx->hE16);
-  CCHECK(hipMemcpy(ctx->dA32, A32, sizeof(A32), hipMemcpyHostToDevice));
-  CCHECK(hipMemcpy(ctx->dB32, B32, sizeof(B32), hipMemcpyHostToDevice));
-  CCHECK(hipMemcpy(ctx->dE32, ctx->hE32, sizeof(ctx->hE32), hipMemcpyHostToDevice));
-  CCHECK(hipMemcpy(ctx->dA8, A8, sizeof(A8), hipMemcpyHostToDevice));
-  CCHECK(hipMemcpy(ctx->dB8, B8, sizeof(B8), hipMemcpyHostToDevice));
-  CCHECK(hipMemcpy(ctx->dE8, ctx->hE8, sizeof(ctx->hE8), hipMemcpyHostToDevice));
-  CCHECK(hipMemcpy(ctx->dA16, A16, sizeof(A16), hipMemcpyHostToDevice));
-  CCHECK(hipMemcpy(ctx->dB16, B16, sizeof(B16), hipMemcpyHostToDevice));
-  CCHECK(hipMemcpy(ctx->dE16, ctx->hE16, sizeof(ctx->hE16), hipMemcpyHostToDevice));
+  CHECK(hipMemcpy(ctx->dA32, A32, sizeof(A32), hipMemcpyHostToDevice));
+  CHECK(hipMemcpy(ctx->dB32, B32, sizeof(B32), hipMemcpyHostToDevice));
+  CHECK(hipMemcpy(ctx->dE32, ctx->hE32, sizeof(ctx->hE32), hipMemcpyHostToDevice));
+  CHECK(hipMemcpy(ctx->dA8, A8, sizeof(A8), hipMemcpyHostToDevice));
+  CHECK(hipMemcpy(ctx->dB8, B8, sizeof(B8), hipMemcpyHostToDevice));
+  CHECK(hipMemcpy(ctx->dE8, ctx->hE8, sizeof(ctx->hE8), hipMemcpyHostToDevice));
+  CHECK(hipMemcpy(ctx->dA16, A16, sizeof(A16), hipMemcpyHostToDevice));
+  CHECK(hipMemcpy(ctx->dB16, B16, sizeof(B16), hipMemcpyHostToDevice));
+  CHECK(hipMemcpy(ctx->dE16, ctx->hE16, sizeof(ctx->hE16), hipMemcpyHostToDevice));
   ctx->seed = seed;
   ctx->tiles_ready = 1;
   return 0;
@@ -423,36 +320,28 @@ int run_compute(int device, const CroComputeOpts* opts, CroComputeResult* out,
     if (o.selftest_elem >= elems[o.selftest_test]) return bad_arg(out, "selftest_elem");
   }
 
-  int count = 0;
-  CCHECK(hipGetDeviceCount(&count));
-  if (device < 0 || device >= count || device >= 64) {
-    snprintf(out->msg, sizeof(out->msg), "device %d out of range (%d present)", device,
-             count);
-    out->rc = -1;
-    return -1;
-  }
-  CovCtx* ctx = &g_cctx[device];
-  std::lock_guard<std::mutex> lock(ctx->mu);
-  CCHECK(hipSetDevice(device));
+  std::unique_lock<std::mutex> lock;
+  CovCtx* ctx = enter_device(g_cctx, device, lock, out->msg, sizeof(out->msg));
+  if (ctx == nullptr) return -1;
   if (!ctx->ready) {
     hipDeviceProp_t prop;
-    CCHECK(hipGetDeviceProperties(&prop, device));
+    CHECK(hipGetDeviceProperties(&prop, device));
     ctx->cus = prop.multiProcessorCount;
-    CCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(coverage_kernel),
+    CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(coverage_kernel),
                                hipFuncAttributeMaxDynamicSharedMemorySize,
                                CRO_COV_MAX_LDS_BYTES));
-    CCHECK(hipEventCreate(&ctx->e0));
-    CCHECK(hipEventCreate(&ctx->e1));
-    CCHECK(hipMalloc(&ctx->dA32, 16 * CRO_COV_F32_K * sizeof(float)));
-    CCHECK(hipMalloc(&ctx->dB32, CRO_COV_F32_K * 16 * sizeof(float)));
-    CCHECK(hipMalloc(&ctx->dE32, sizeof(ctx->hE32)));
-    CCHECK(hipMalloc(&ctx->dA8, 16 * CRO_COV_I8_K));
-    CCHECK(hipMalloc(&ctx->dB8, CRO_COV_I8_K * 16));
-    CCHECK(hipMalloc(&ctx->dE8, sizeof(ctx->hE8)));
-    CCHECK(hipMalloc(&ctx->dA16, 32 * CRO_COV_BF16_K * sizeof(uint16_t)));
-    CCHECK(hipMalloc(&ctx->dB16, CRO_COV_BF16_K * 32 * sizeof(uint16_t)));
-    CCHECK(hipMalloc(&ctx->dE16, sizeof(ctx->hE16)));
-    CCHECK(hipMalloc(&ctx->dEx, sizeof(ctx->hE16)));  // the largest tile
+    CHECK(hipEventCreate(&ctx->e0));
+    CHECK(hipEventCreate(&ctx->e1));
+    CHECK(hipMalloc(&ctx->dA32, 16 * CRO_COV_F32_K * sizeof(float)));
+    CHECK(hipMalloc(&ctx->dB32, CRO_COV_F32_K * 16 * sizeof(float)));
+    CHECK(hipMalloc(&ctx->dE32, sizeof(ctx->hE32)));
+    CHECK(hipMalloc(&ctx->dA8, 16 * CRO_COV_I8_K));
+    CHECK(hipMalloc(&ctx->dB8, CRO_COV_I8_K * 16));
+    CHECK(hipMalloc(&ctx->dE8, sizeof(ctx->hE8)));
+    CHECK(hipMalloc(&ctx->dA16, 32 * CRO_COV_BF16_K * sizeof(uint16_t)));
+    CHECK(hipMalloc(&ctx->dB16, CRO_COV_BF16_K * 32 * sizeof(uint16_t)));
+    CHECK(hipMalloc(&ctx->dE16, sizeof(ctx->hE16)));
+    CHECK(hipMalloc(&ctx->dEx, sizeof(ctx->hE16)));  // the largest tile
     ctx->ready = 1;
   }
   if (!ctx->tiles_ready || ctx->seed != o.seed) {
@@ -467,7 +356,7 @@ int run_compute(int device, const CroComputeOpts* opts, CroComputeResult* out,
     if (ctx->d_records) (void)hipFree(ctx->d_records);
     ctx->d_records = nullptr;
     ctx->records_cap = 0;
-    CCHECK(hipMalloc(&ctx->d_records, n_max * sizeof(CroCoverageRecord)));
+    CHECK(hipMalloc(&ctx->d_records, n_max * sizeof(CroCoverageRecord)));
     ctx->records_cap = n_max;
   }
   out->cus_expected = ctx->cus;
@@ -511,24 +400,22 @@ int run_compute(int device, const CroComputeOpts* opts, CroComputeResult* out,
       p.E16 = (const float*)ctx->dEx;
     }
     alt[o.selftest_elem] ^= p.inj_flip;
-    CCHECK(hipMemcpy(ctx->dEx, alt, bytes, hipMemcpyHostToDevice));
+    CHECK(hipMemcpy(ctx->dEx, alt, bytes, hipMemcpyHostToDevice));
   }
 
   std::vector<CroCoverageRecord> records(n_max);
-  CCHECK(hipMemset(ctx->d_records, 0, n_max * sizeof(CroCoverageRecord)));
+  CHECK(hipMemset(ctx->d_records, 0, n_max * sizeof(CroCoverageRecord)));
   int rounds = 0;
   double gpu_ms = 0.0;
   for (;;) {
     p.records = ctx->d_records + (size_t)rounds * per_round;
-    CCHECK(hipEventRecord(ctx->e0));
-    hipLaunchKernelGGL(coverage_kernel, dim3(grid), dim3(kBlock), (size_t)lds_bytes, 0, p);
-    CCHECK(hipGetLastError());
-    CCHECK(hipEventRecord(ctx->e1));
-    CCHECK(hipEventSynchronize(ctx->e1));
+    const auto one_round = [&] {
+      hipLaunchKernelGGL(coverage_kernel, dim3(grid), dim3(kBlock), (size_t)lds_bytes, 0, p);
+    };
     float ms = 0.f;
-    CCHECK(hipEventElapsedTime(&ms, ctx->e0, ctx->e1));
+    CHECK(timed_ms(*ctx, &ms, one_round));
     gpu_ms += ms;
-    CCHECK(hipMemcpy(records.data() + (size_t)rounds * per_round, p.records,
+    CHECK(hipMemcpy(records.data() + (size_t)rounds * per_round, p.records,
                      per_round * sizeof(CroCoverageRecord), hipMemcpyDeviceToHost));
     ++rounds;
     cro_coverage_aggregate(records.data(), (size_t)rounds * per_round, ctx->cus, &out->agg);
@@ -546,12 +433,10 @@ int run_compute(int device, const CroComputeOpts* opts, CroComputeResult* out,
   const CroCoverageAgg& a = out->agg;
   if (a.waves_run != n) {
     // a wave that never wrote its record: the launch did not run to the end
-    out->rc = -1;
     snprintf(out->msg, sizeof(out->msg), "%llu of %zu waves reported", a.waves_run, n);
     return -1;
   }
   if (a.waves_bad) {
-    out->rc = -30;
     out->first_bad_round = (int)((size_t)a.first_bad_index / per_round);
     out->first_bad_record = (int)((size_t)a.first_bad_index % per_round);
     snprintf(out->failed_test, sizeof(out->failed_test), "%s",
@@ -564,7 +449,6 @@ int run_compute(int device, const CroComputeOpts* opts, CroComputeResult* out,
     return -30;
   }
   if (o.min_cu_fraction > 0.0 && (double)a.cus_seen < o.min_cu_fraction * (double)ctx->cus) {
-    out->rc = -31;
     snprintf(out->msg, sizeof(out->msg),
              "coverage %d of %d CUs after %d rounds is below the floor %.3f", a.cus_seen,
              ctx->cus, rounds, o.min_cu_fraction);
@@ -587,9 +471,9 @@ extern "C" int cro_probe_compute_records(int device, const struct CroComputeOpts
   out->agg.xcd = out->agg.se = out->agg.sh = out->agg.cu = out->agg.simd = -1;
   out->agg.first_bad = ~0u;
   const double t0 = now_ms();
-  const int rc = run_compute(device, opts, out, records_out, max_records);
+  out->rc = run_compute(device, opts, out, records_out, max_records);
   out->t_total_ms = now_ms() - t0;
-  return rc;
+  return out->rc;
 }
 
 extern "C" int cro_probe_compute(int device, const struct CroComputeOpts* opts,
@@ -607,19 +491,17 @@ extern "C" int cro_probe_mfma_tile(int device, int kind, const void* A, const vo
   const size_t esz = kind == 1 ? 1 : 2;
   const size_t in_bytes = (size_t)rows * K * esz, out_bytes = (size_t)rows * rows * 4;
   if (hipSetDevice(device) != hipSuccess) return -1;
-  void *dA = nullptr, *dB = nullptr, *dD = nullptr;
-  hipError_t e = hipMalloc(&dA, in_bytes);
-  if (e == hipSuccess) e = hipMalloc(&dB, in_bytes);
-  if (e == hipSuccess) e = hipMalloc(&dD, out_bytes);
-  if (e == hipSuccess) e = hipMemcpy(dA, A, in_bytes, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dB, B, in_bytes, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(mfma_tile_kernel, dim3(1), dim3(64), 0, 0, kind, dA, dB, dD, K);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpy(D, dD, out_bytes, hipMemcpyDeviceToHost);
-  if (dA) (void)hipFree(dA);
-  if (dB) (void)hipFree(dB);
-  if (dD) (void)hipFree(dD);
-  return e == hipSuccess ? 0 : -1;
+  DevBuf<void> dA, dB, dD;
+  const auto run = [&]() -> hipError_t {
+    TRY(dA.alloc(in_bytes));
+    TRY(dB.alloc(in_bytes));
+    TRY(dD.alloc(out_bytes));
+    TRY(hipMemcpy(dA.get(), A, in_bytes, hipMemcpyHostToDevice));
+    TRY(hipMemcpy(dB.get(), B, in_bytes, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(mfma_tile_kernel, dim3(1), dim3(64), 0, 0, kind, dA.get(), dB.get(),
+                       dD.get(), K);
+    TRY(hipGetLastError());
+    return hipMemcpy(D, dD.get(), out_bytes, hipMemcpyDeviceToHost);
+  };
+  return run() == hipSuccess ? 0 : -1;
 }

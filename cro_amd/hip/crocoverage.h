@@ -182,9 +182,9 @@ static inline void cro_coverage_aggregate(const CroCoverageRecord* records, size
 }
 
 // -- inputs and expected tiles ----------------------------------------------------
-// All three input sets come from the quick probe's LCG (probe.hip) so the
-// numpy mirror is a few lines; seed 0 gives the f32 check the quick probe's
-// own inputs.
+// All three input sets come from one LCG so the numpy mirror is a few lines.
+// The quick probe (probe.hip) takes its inputs and expected tile from here
+// too: cro_cov_make_f32 at seed 0 and cro_cov_ref_f32.
 
 static inline uint32_t cro_cov_lcg(uint32_t* s) {
   *s = *s * 1664525u + 1013904223u;
@@ -201,7 +201,7 @@ static inline void cro_cov_make_f32(uint32_t seed, float* A, float* B) {
 }
 
 // gfx950's f32-input MFMA is bitwise a k-ordered fmaf chain, so this tile is
-// compared exactly (as host_mfma_ref in probe.hip).
+// compared exactly.
 static inline void cro_cov_ref_f32(const float* A, const float* B, float* D) {
   for (int r = 0; r < 16; ++r)
     for (int c = 0; c < 16; ++c) {

@@ -3,7 +3,8 @@
 // One definition shared by the device kernels (integrity.hip), the host
 // side of the link stages and the host-only parity test, so "what the GPU
 // wrote" and "what the host expects" cannot drift apart.  Plain C++: a host
-// compiler without HIP can include it.
+// compiler without HIP can include it (the 16-byte vector form at the end is
+// for hipcc only; coverage.hip's LDS march uses it too).
 //
 // The 32-bit word at global word index w (64-bit) under a 32-bit seed:
 //
@@ -45,3 +46,18 @@ CRO_PATTERN_HD static inline uint32_t cro_pattern_word(uint64_t w, uint32_t seed
   x = cro_pattern_mix32(x);
   return invert ? ~x : x;
 }
+
+#ifdef __HIPCC__
+#include <hip/hip_runtime.h>
+
+// words w .. w + 3 as the 16-byte vector the kernels store and compare
+CRO_PATTERN_HD static inline uint4 cro_pattern_vec4(uint64_t w, uint32_t seed,
+                                                    uint32_t invert) {
+  uint4 v;
+  v.x = cro_pattern_word(w + 0, seed, invert);
+  v.y = cro_pattern_word(w + 1, seed, invert);
+  v.z = cro_pattern_word(w + 2, seed, invert);
+  v.w = cro_pattern_word(w + 3, seed, invert);
+  return v;
+}
+#endif

@@ -1,5 +1,6 @@
 // Shared C ABI for the gfx950 health probe library (libcroprobe.so).
-// Consumers: probe.hip, integrity.hip and coverage.hip (implementation),
+// Consumers: probe.hip, integrity.hip and coverage.hip (implementation; their
+// shared internals are in crohost.h and cromfma.h, which nothing else includes),
 // agent/croagent.cpp (native CLI),
 // nodeops/probe.py (ctypes — keep CroProbeResult field order in sync there).
 #pragma once

@@ -16,15 +16,14 @@
 // pointers.  Gates are on data (any mismatch or HIP error fails); rates are
 // reported, and gated only by the optional link_floor_gbps.
 //
-// Compiled with probe.hip into libcroprobe.so (cro_amd/hip/build.py).
+// Compiled with probe.hip and coverage.hip into libcroprobe.so
+// (cro_amd/hip/build.py); host plumbing shared with them in crohost.h.
 
 #include <hip/hip_runtime.h>
-#include <chrono>
-#include <cstdio>
 #include <cstring>
-#include <mutex>
 #include <vector>
 
+#include "crohost.h"
 #include "cropattern.h"
 #include "croprobe.h"
 
@@ -37,7 +36,6 @@ struct PatternReport {
   unsigned int pad;
 };
 
-constexpr int kBlock = 256;
 // 1024 workgroups x 256 lanes x 16 B = 16 MiB (2^20 vectors) per grid pass:
 // 4 workgroups on each of the 256 CUs, grid-stride for the rest.
 constexpr unsigned kMaxGrid = 1024;
@@ -54,13 +52,7 @@ __global__ __launch_bounds__(kBlock) void pattern_fill_kernel(
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   uint4* __restrict__ d4 = reinterpret_cast<uint4*>(dst);
   for (uint64_t i = tid; i < n4; i += stride) {
-    const uint64_t w = base_word + (i << 2);
-    uint4 v;
-    v.x = cro_pattern_word(w + 0, seed, invert);
-    v.y = cro_pattern_word(w + 1, seed, invert);
-    v.z = cro_pattern_word(w + 2, seed, invert);
-    v.w = cro_pattern_word(w + 3, seed, invert);
-    d4[i] = v;
+    d4[i] = cro_pattern_vec4(base_word + (i << 2), seed, invert);
   }
   const uint64_t tail0 = n4 << 2;  // n_words % 4 trailing words, one lane each
   if (tid < n_words - tail0)
@@ -89,12 +81,7 @@ __global__ __launch_bounds__(kBlock) void pattern_verify_kernel(
 
   for (uint64_t i0 = tid - lane; i0 < n4; i0 += stride) {
     const uint64_t i = i0 + lane;
-    const uint64_t w = base_word + (i << 2);
-    uint4 want;
-    want.x = cro_pattern_word(w + 0, seed, invert);
-    want.y = cro_pattern_word(w + 1, seed, invert);
-    want.z = cro_pattern_word(w + 2, seed, invert);
-    want.w = cro_pattern_word(w + 3, seed, invert);
+    const uint4 want = cro_pattern_vec4(base_word + (i << 2), seed, invert);
     uint4 got = want;  // lanes past the end compare equal
     if (i < n4) got = s4[i];
     const uint32_t d[4] = {got.x ^ want.x, got.y ^ want.y, got.z ^ want.z,
@@ -141,12 +128,6 @@ __global__ __launch_bounds__(kBlock) void pattern_verify_kernel(
 // host side
 // ---------------------------------------------------------------------------
 
-double now_ms() {
-  return std::chrono::duration<double, std::milli>(
-             std::chrono::steady_clock::now().time_since_epoch())
-      .count();
-}
-
 unsigned grid_for(uint64_t n_words) {
   uint64_t blocks = ((n_words >> 2) + kBlock - 1) / kBlock;
   if (blocks < 1) blocks = 1;  // the tail still needs one workgroup
@@ -186,47 +167,19 @@ PatternReport host_verify(const uint32_t* src, uint64_t n_words, uint32_t seed,
 
 const PatternReport kCleanReport = {0, ~0ull, 0, 0};
 
-// Per-device cached context (as ProbeCtx in probe.hip): the pinned link
-// buffer, the events and the report word survive between attaches; VRAM
-// does not.  The mutex serialises concurrent reconcile workers on one
-// device.
-struct IntegCtx {
-  std::mutex mu;
-  int ready = 0;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
+// Per-device cached context (CtxBase, crohost.h): the pinned link buffer, the
+// events and the report word survive between attaches; VRAM does not.
+struct IntegCtx : CtxBase {
   PatternReport* d_report = nullptr;
   uint32_t* pinned = nullptr;      // host address
   uint32_t* pinned_dev = nullptr;  // the same memory as the device sees it
   size_t pinned_bytes = 0;
 };
-IntegCtx g_ictx[64];
-
-// VRAM held by one run; released on every way out.
-struct Held {
-  std::vector<uint32_t*> chunks;
-  uint32_t* dlink = nullptr;
-  ~Held() {
-    for (uint32_t* p : chunks) (void)hipFree(p);
-    if (dlink) (void)hipFree(dlink);
-  }
-};
-
-#define ICHECK(expr)                                                         \
-  do {                                                                       \
-    hipError_t _e = (expr);                                                  \
-    if (_e != hipSuccess) {                                                  \
-      snprintf(out->msg, sizeof(out->msg), "%s failed: %s", #expr,           \
-               hipGetErrorString(_e));                                       \
-      out->ok = 0;                                                           \
-      out->rc = -1;                                                          \
-      return -1;                                                             \
-    }                                                                        \
-  } while (0)
+IntegCtx g_ictx[kMaxDevices];
 
 int fail_data(CroIntegrityResult* out, const char* stage, const PatternReport& r,
               unsigned long long stage_base_word) {
   out->ok = 0;
-  out->rc = -20;
   out->n_bad = r.n_bad;
   out->first_bad_byte = (r.first_bad - stage_base_word) * 4ull;
   out->bits_bad = r.bits_bad;
@@ -255,26 +208,18 @@ int run_integrity(int device, const CroIntegrityOpts* opts, CroIntegrityResult* 
   const uint64_t link_words = (uint64_t)link_bytes >> 2;
   const uint64_t chunk_words = (uint64_t)chunk_bytes >> 2;
 
-  int count = 0;
-  ICHECK(hipGetDeviceCount(&count));
-  if (device < 0 || device >= count || device >= 64) {
-    snprintf(out->msg, sizeof(out->msg), "device %d out of range (%d present)", device,
-             count);
-    out->rc = -1;
-    return -1;
-  }
+  std::unique_lock<std::mutex> lock;
+  IntegCtx* ctx = enter_device(g_ictx, device, lock, out->msg, sizeof(out->msg));
+  if (ctx == nullptr) return -1;
+  // after the ordinal, as ever: a bad device is what the message names first
   if (vram_words == 0 || link_words == 0) {
     snprintf(out->msg, sizeof(out->msg), "vram_bytes and link_bytes must be >= 4");
-    out->rc = -1;
     return -1;
   }
-  IntegCtx* ctx = &g_ictx[device];
-  std::lock_guard<std::mutex> lock(ctx->mu);
-  ICHECK(hipSetDevice(device));
   if (!ctx->ready) {
-    ICHECK(hipEventCreate(&ctx->e0));
-    ICHECK(hipEventCreate(&ctx->e1));
-    ICHECK(hipMalloc(&ctx->d_report, sizeof(PatternReport)));
+    CHECK(hipEventCreate(&ctx->e0));
+    CHECK(hipEventCreate(&ctx->e1));
+    CHECK(hipMalloc(&ctx->d_report, sizeof(PatternReport)));
     ctx->ready = 1;
   }
   if (ctx->pinned_bytes < link_words * 4) {
@@ -284,63 +229,58 @@ int run_integrity(int device, const CroIntegrityOpts* opts, CroIntegrityResult* 
       ctx->pinned_dev = nullptr;
       ctx->pinned_bytes = 0;
     }
-    ICHECK(hipHostMalloc(&ctx->pinned, link_words * 4, hipHostMallocMapped));
-    ICHECK(hipHostGetDevicePointer((void**)&ctx->pinned_dev, ctx->pinned, 0));
+    CHECK(hipHostMalloc(&ctx->pinned, link_words * 4, hipHostMallocMapped));
+    CHECK(hipHostGetDevicePointer((void**)&ctx->pinned_dev, ctx->pinned, 0));
     ctx->pinned_bytes = link_words * 4;
     // one untimed round trip with the new buffer: the first copy of a
     // process pays one-time set-up that would understate h2d_dma_gbps
     const size_t warm = link_words * 4 < (1u << 20) ? link_words * 4 : (1u << 20);
-    void* tmp = nullptr;
-    ICHECK(hipMalloc(&tmp, warm));
-    hipError_t we = hipMemcpy(tmp, ctx->pinned, warm, hipMemcpyHostToDevice);
-    if (we == hipSuccess) we = hipMemcpy(ctx->pinned, tmp, warm, hipMemcpyDeviceToHost);
-    (void)hipFree(tmp);
-    ICHECK(we);
+    DevBuf<void> tmp;
+    CHECK(tmp.alloc(warm));
+    CHECK(hipMemcpy(tmp.get(), ctx->pinned, warm, hipMemcpyHostToDevice));
+    CHECK(hipMemcpy(ctx->pinned, tmp.get(), warm, hipMemcpyDeviceToHost));
   }
-  hipEvent_t e0 = ctx->e0, e1 = ctx->e1;
   PatternReport rep;
   float ms = 0.f;
-  Held held;
+  // VRAM held by this run; released on every way out
+  std::vector<DevBuf<uint32_t>> chunks;
+  DevBuf<uint32_t> dlink;
 
   // -- VRAM ------------------------------------------------------------------
   double t0 = now_ms();
   std::vector<uint64_t> chunk_n;
   for (uint64_t done = 0; done < vram_words;) {
     const uint64_t n = vram_words - done < chunk_words ? vram_words - done : chunk_words;
-    uint32_t* p = nullptr;
-    ICHECK(hipMalloc(&p, (n * 4 + 15) & ~15ull));
-    held.chunks.push_back(p);
+    chunks.emplace_back();
+    CHECK(chunks.back().alloc((n * 4 + 15) & ~15ull));
     chunk_n.push_back(n);
     done += n;
   }
-  out->vram_chunks = (int)held.chunks.size();
+  out->vram_chunks = (int)chunks.size();
   float fill_ms = 0.f, verify_ms = 0.f;
   for (uint32_t invert = 0; invert < 2; ++invert) {
-    ICHECK(hipEventRecord(e0));
-    uint64_t base = 0;
-    for (size_t c = 0; c < held.chunks.size(); ++c) {
-      launch_fill(held.chunks[c], chunk_n[c], base, seed, invert);
-      base += chunk_n[c];
-    }
-    ICHECK(hipGetLastError());
-    ICHECK(hipEventRecord(e1));
-    ICHECK(hipEventSynchronize(e1));
-    ICHECK(hipEventElapsedTime(&ms, e0, e1));
+    // every chunk in one timed window, at its place in the span's word count
+    const auto fill_all = [&] {
+      uint64_t base = 0;
+      for (size_t c = 0; c < chunks.size(); ++c) {
+        launch_fill(chunks[c].get(), chunk_n[c], base, seed, invert);
+        base += chunk_n[c];
+      }
+    };
+    const auto verify_all = [&] {
+      uint64_t base = 0;
+      for (size_t c = 0; c < chunks.size(); ++c) {
+        launch_verify(chunks[c].get(), chunk_n[c], base, seed, invert, ctx->d_report);
+        base += chunk_n[c];
+      }
+    };
+    CHECK(timed_ms(*ctx, &ms, fill_all));
     fill_ms += ms;
 
-    ICHECK(hipMemcpy(ctx->d_report, &kCleanReport, sizeof(rep), hipMemcpyHostToDevice));
-    ICHECK(hipEventRecord(e0));
-    base = 0;
-    for (size_t c = 0; c < held.chunks.size(); ++c) {
-      launch_verify(held.chunks[c], chunk_n[c], base, seed, invert, ctx->d_report);
-      base += chunk_n[c];
-    }
-    ICHECK(hipGetLastError());
-    ICHECK(hipEventRecord(e1));
-    ICHECK(hipEventSynchronize(e1));
-    ICHECK(hipEventElapsedTime(&ms, e0, e1));
+    CHECK(hipMemcpy(ctx->d_report, &kCleanReport, sizeof(rep), hipMemcpyHostToDevice));
+    CHECK(timed_ms(*ctx, &ms, verify_all));
     verify_ms += ms;
-    ICHECK(hipMemcpy(&rep, ctx->d_report, sizeof(rep), hipMemcpyDeviceToHost));
+    CHECK(hipMemcpy(&rep, ctx->d_report, sizeof(rep), hipMemcpyDeviceToHost));
     out->vram_passes = (int)invert + 1;
     out->vram_bytes_verified += (long long)(vram_words * 4);
     out->vram_n_bad += rep.n_bad;
@@ -348,71 +288,63 @@ int run_integrity(int device, const CroIntegrityOpts* opts, CroIntegrityResult* 
   }
   out->vram_fill_gbps = gbps(2.0 * vram_words * 4, fill_ms);
   out->vram_verify_gbps = gbps(2.0 * vram_words * 4, verify_ms);
-  for (uint32_t* p : held.chunks) ICHECK(hipFree(p));
-  held.chunks.clear();
+  for (DevBuf<uint32_t>& chunk : chunks) CHECK(chunk.free());
+  chunks.clear();
   out->t_vram_ms = now_ms() - t0;
 
   // -- link, copy engines ------------------------------------------------------
+  // (a copy that fails inside a timed window is what timed_ms reports)
   t0 = now_ms();
   const double lbytes = (double)(link_words * 4);
-  ICHECK(hipMalloc(&held.dlink, (link_words * 4 + 15) & ~15ull));
+  CHECK(dlink.alloc((link_words * 4 + 15) & ~15ull));
   host_fill(ctx->pinned, link_words, seed, 0);
-  ICHECK(hipEventRecord(e0));
-  ICHECK(hipMemcpy(held.dlink, ctx->pinned, link_words * 4, hipMemcpyHostToDevice));
-  ICHECK(hipEventRecord(e1));
-  ICHECK(hipEventSynchronize(e1));
-  ICHECK(hipEventElapsedTime(&ms, e0, e1));
+  const auto h2d_copy = [&] {
+    (void)hipMemcpy(dlink.get(), ctx->pinned, link_words * 4, hipMemcpyHostToDevice);
+  };
+  CHECK(timed_ms(*ctx, &ms, h2d_copy));
   out->h2d_dma_gbps = gbps(lbytes, ms);
-  ICHECK(hipMemcpy(ctx->d_report, &kCleanReport, sizeof(rep), hipMemcpyHostToDevice));
-  launch_verify(held.dlink, link_words, 0, seed, 0, ctx->d_report);
-  ICHECK(hipGetLastError());
-  ICHECK(hipMemcpy(&rep, ctx->d_report, sizeof(rep), hipMemcpyDeviceToHost));
+  CHECK(hipMemcpy(ctx->d_report, &kCleanReport, sizeof(rep), hipMemcpyHostToDevice));
+  launch_verify(dlink.get(), link_words, 0, seed, 0, ctx->d_report);
+  CHECK(hipGetLastError());
+  CHECK(hipMemcpy(&rep, ctx->d_report, sizeof(rep), hipMemcpyDeviceToHost));
   out->link_passes = 1;
   out->h2d_dma_bytes_verified = (long long)(link_words * 4);
   out->h2d_dma_n_bad = rep.n_bad;
   if (rep.n_bad) return fail_data(out, "h2d_dma", rep, 0);
 
-  launch_fill(held.dlink, link_words, 0, seed_back, 0);
-  ICHECK(hipGetLastError());
-  ICHECK(hipDeviceSynchronize());
-  ICHECK(hipEventRecord(e0));
-  ICHECK(hipMemcpy(ctx->pinned, held.dlink, link_words * 4, hipMemcpyDeviceToHost));
-  ICHECK(hipEventRecord(e1));
-  ICHECK(hipEventSynchronize(e1));
-  ICHECK(hipEventElapsedTime(&ms, e0, e1));
+  launch_fill(dlink.get(), link_words, 0, seed_back, 0);
+  CHECK(hipGetLastError());
+  CHECK(hipDeviceSynchronize());
+  const auto d2h_copy = [&] {
+    (void)hipMemcpy(ctx->pinned, dlink.get(), link_words * 4, hipMemcpyDeviceToHost);
+  };
+  CHECK(timed_ms(*ctx, &ms, d2h_copy));
   out->d2h_dma_gbps = gbps(lbytes, ms);
   rep = host_verify(ctx->pinned, link_words, seed_back, 0);
   out->d2h_dma_bytes_verified = (long long)(link_words * 4);
   out->d2h_dma_n_bad = rep.n_bad;
   if (rep.n_bad) return fail_data(out, "d2h_dma", rep, 0);
-  ICHECK(hipFree(held.dlink));
-  held.dlink = nullptr;
+  CHECK(dlink.free());
   out->t_link_dma_ms = now_ms() - t0;
 
   // -- link, shader loads and stores (complement pattern) ----------------------
   t0 = now_ms();
   host_fill(ctx->pinned, link_words, seed, 1);
-  ICHECK(hipMemcpy(ctx->d_report, &kCleanReport, sizeof(rep), hipMemcpyHostToDevice));
-  ICHECK(hipEventRecord(e0));
-  launch_verify(ctx->pinned_dev, link_words, 0, seed, 1, ctx->d_report);
-  ICHECK(hipGetLastError());
-  ICHECK(hipEventRecord(e1));
-  ICHECK(hipEventSynchronize(e1));
-  ICHECK(hipEventElapsedTime(&ms, e0, e1));
+  CHECK(hipMemcpy(ctx->d_report, &kCleanReport, sizeof(rep), hipMemcpyHostToDevice));
+  const auto h2d_verify = [&] {
+    launch_verify(ctx->pinned_dev, link_words, 0, seed, 1, ctx->d_report);
+  };
+  CHECK(timed_ms(*ctx, &ms, h2d_verify));
   out->h2d_kernel_gbps = gbps(lbytes, ms);
-  ICHECK(hipMemcpy(&rep, ctx->d_report, sizeof(rep), hipMemcpyDeviceToHost));
+  CHECK(hipMemcpy(&rep, ctx->d_report, sizeof(rep), hipMemcpyDeviceToHost));
   out->h2d_kernel_bytes_verified = (long long)(link_words * 4);
   out->h2d_kernel_n_bad = rep.n_bad;
   if (rep.n_bad) return fail_data(out, "h2d_kernel", rep, 0);
 
-  ICHECK(hipEventRecord(e0));
-  launch_fill(ctx->pinned_dev, link_words, 0, seed_back, 1);
-  ICHECK(hipGetLastError());
-  ICHECK(hipEventRecord(e1));
-  ICHECK(hipEventSynchronize(e1));
-  ICHECK(hipEventElapsedTime(&ms, e0, e1));
+  const auto d2h_fill = [&] { launch_fill(ctx->pinned_dev, link_words, 0, seed_back, 1); };
+  CHECK(timed_ms(*ctx, &ms, d2h_fill));
   out->d2h_kernel_gbps = gbps(lbytes, ms);
-  ICHECK(hipDeviceSynchronize());
+  CHECK(hipDeviceSynchronize());
   rep = host_verify(ctx->pinned, link_words, seed_back, 1);
   out->d2h_kernel_bytes_verified = (long long)(link_words * 4);
   out->d2h_kernel_n_bad = rep.n_bad;
@@ -425,7 +357,6 @@ int run_integrity(int device, const CroIntegrityOpts* opts, CroIntegrityResult* 
         {"h2d_kernel", out->h2d_kernel_gbps}, {"d2h_kernel", out->d2h_kernel_gbps}};
     for (const auto& r : rates) {
       if (r.rate < floor_gbps) {
-        out->rc = -21;
         snprintf(out->failed_stage, sizeof(out->failed_stage), "%s", r.stage);
         snprintf(out->msg, sizeof(out->msg),
                  "link rate %.1f GB/s in stage %s below floor %.1f GB/s", r.rate, r.stage,
@@ -446,9 +377,9 @@ extern "C" int cro_probe_integrity(int device, const struct CroIntegrityOpts* op
   memset(out, 0, sizeof(*out));
   out->first_bad_byte = ~0ull;
   const double t0 = now_ms();
-  int rc = run_integrity(device, opts, out);
+  out->rc = run_integrity(device, opts, out);
   out->t_total_ms = now_ms() - t0;
-  return rc;
+  return out->rc;
 }
 
 extern "C" int cro_probe_pattern_fill(int device, unsigned int seed, int invert,
@@ -456,13 +387,11 @@ extern "C" int cro_probe_pattern_fill(int device, unsigned int seed, int invert,
                                       unsigned long long n_words, unsigned int* host_out) {
   if (n_words == 0 || host_out == nullptr) return -10;
   if (hipSetDevice(device) != hipSuccess) return -1;
-  uint32_t* d = nullptr;
-  if (hipMalloc(&d, (n_words * 4 + 15) & ~15ull) != hipSuccess) return -1;
-  launch_fill(d, n_words, base_word, seed, invert ? 1u : 0u);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpy(host_out, d, n_words * 4, hipMemcpyDeviceToHost);
-  (void)hipFree(d);
-  return e == hipSuccess ? 0 : -1;
+  DevBuf<uint32_t> d;
+  if (d.alloc((n_words * 4 + 15) & ~15ull) != hipSuccess) return -1;
+  launch_fill(d.get(), n_words, base_word, seed, invert ? 1u : 0u);
+  if (hipGetLastError() != hipSuccess) return -1;
+  return hipMemcpy(host_out, d.get(), n_words * 4, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
 }
 
 extern "C" int cro_probe_pattern_verify(int device, unsigned int seed, int invert,
@@ -474,21 +403,19 @@ extern "C" int cro_probe_pattern_verify(int device, unsigned int seed, int inver
                                         unsigned int* bits_bad) {
   if (n_words == 0 || host_in == nullptr) return -10;
   if (hipSetDevice(device) != hipSuccess) return -1;
-  uint32_t* d = nullptr;
-  PatternReport* d_rep = nullptr;
+  DevBuf<uint32_t> d;
+  DevBuf<PatternReport> d_rep;
   PatternReport rep = kCleanReport;
-  hipError_t e = hipMalloc(&d, (n_words * 4 + 15) & ~15ull);
-  if (e == hipSuccess) e = hipMalloc(&d_rep, sizeof(rep));
-  if (e == hipSuccess) e = hipMemcpy(d, host_in, n_words * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_rep, &rep, sizeof(rep), hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    launch_verify(d, n_words, base_word, seed, invert ? 1u : 0u, d_rep);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpy(&rep, d_rep, sizeof(rep), hipMemcpyDeviceToHost);
-  if (d) (void)hipFree(d);
-  if (d_rep) (void)hipFree(d_rep);
-  if (e != hipSuccess) return -1;
+  const auto run = [&]() -> hipError_t {
+    TRY(d.alloc((n_words * 4 + 15) & ~15ull));
+    TRY(d_rep.alloc(sizeof(rep)));
+    TRY(hipMemcpy(d.get(), host_in, n_words * 4, hipMemcpyHostToDevice));
+    TRY(hipMemcpy(d_rep.get(), &rep, sizeof(rep), hipMemcpyHostToDevice));
+    launch_verify(d.get(), n_words, base_word, seed, invert ? 1u : 0u, d_rep.get());
+    TRY(hipGetLastError());
+    return hipMemcpy(&rep, d_rep.get(), sizeof(rep), hipMemcpyDeviceToHost);
+  };
+  if (run() != hipSuccess) return -1;
   if (n_bad) *n_bad = rep.n_bad;
   if (first_bad) *first_bad = rep.first_bad;
   if (bits_bad) *bits_bad = rep.bits_bad;

@@ -19,8 +19,10 @@
 //      independent accumulators per wave; reports matrix-core TFLOP/s
 //      (healthy ≈2.3-2.5 PF; loose floor gate).
 //
-// Built standalone with hipcc for gfx950 only (no torch dependency):
-//   hipcc --offload-arch=gfx950 -O3 -fPIC -shared probe.hip -o libcroprobe.so
+// Built with hipcc for gfx950 only (no torch dependency), with integrity.hip
+// and coverage.hip, into libcroprobe.so (cro_amd/hip/build.py).  The three
+// sources share their host plumbing (crohost.h) and, probe.hip and
+// coverage.hip, the wave-level matrix code (cromfma.h).
 //
 // C ABI consumed by cro_amd/nodeops/probe.py via ctypes.  Besides the probe
 // itself it has one raw entry per kernel (caller data in, raw output back)
@@ -29,56 +31,24 @@
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
-#include <chrono>
-#include <cstdio>
 #include <cstring>
-#include <mutex>
 #include <vector>
 
-static double now_ms() {
-  return std::chrono::duration<double, std::milli>(
-             std::chrono::steady_clock::now().time_since_epoch())
-      .count();
-}
-
-#define CHECK(expr)                                                          \
-  do {                                                                       \
-    hipError_t _e = (expr);                                                  \
-    if (_e != hipSuccess) {                                                  \
-      snprintf(out->msg, sizeof(out->msg), "%s failed: %s", #expr,           \
-               hipGetErrorString(_e));                                       \
-      out->ok = 0;                                                           \
-      return -1;                                                             \
-    }                                                                        \
-  } while (0)
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
+#include "crohost.h"
+#include "cromfma.h"
 #include "croprobe.h"
 
 // ---------------------------------------------------------------------------
-// 1. exact f32 MFMA check (v_mfma_f32_16x16x4_f32: A 16x4, B 4x16, D 16x16;
-//    lane l holds A[l&15][l>>4], B[l>>4][l&15]; D reg r -> row (l>>4)*4+r,
-//    col l&15 — layouts per cdna_hip_programming.md §3)
+// 1. exact f32 MFMA check (v_mfma_f32_16x16x4_f32: A 16xK, B Kx16, D 16x16;
+//    lane maps in cromfma.h, layouts per cdna_hip_programming.md §3)
 // ---------------------------------------------------------------------------
 
 __global__ void mfma_f32_check_kernel(const float* __restrict__ A,
                                       const float* __restrict__ B,
                                       float* __restrict__ D, int K) {
-  int lane = threadIdx.x;  // exactly one wave of 64
-  int row = lane & 15;
-  int kh = lane >> 4;  // which of the 4 k slots this lane carries
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  for (int k0 = 0; k0 < K; k0 += 4) {
-    float a = A[row * K + (k0 + kh)];
-    float b = B[(k0 + kh) * 16 + row];  // col index == lane&15 == row bits
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);
-  }
-  for (int r = 0; r < 4; ++r) {
-    D[((lane >> 4) * 4 + r) * 16 + (lane & 15)] = acc[r];
-  }
+  const uint32_t lane = threadIdx.x;  // exactly one wave of 64
+  const f32x4 acc = wave_mfma_f32(A, B, K, lane);
+  for (int r = 0; r < 4; ++r) D[mfma_elem16(lane, r)] = acc[r];
 }
 
 // ---------------------------------------------------------------------------
@@ -131,41 +101,22 @@ __global__ void mfma_bf16_rate_kernel(float* __restrict__ out, int iters) {
 // host driver
 // ---------------------------------------------------------------------------
 
-static void host_mfma_ref(const float* A, const float* B, float* D, int K) {
-  // gfx950 f32-in MFMA is bitwise a k-ordered fmaf chain (guide §3):
-  for (int r = 0; r < 16; ++r) {
-    for (int c = 0; c < 16; ++c) {
-      float acc = 0.f;
-      for (int k = 0; k < K; ++k) acc = fmaf(A[r * K + k], B[k * 16 + c], acc);
-      D[r * 16 + c] = acc;
-    }
-  }
-}
-
-// Per-device cached probe context: the probe runs on every attach, so
-// allocations and events are created once and reused — only the kernels,
-// copies and compares run per call.  The mutex serialises concurrent
-// reconcile workers on one device: without it two first calls both allocate,
-// and any two calls share e0/e1.
-struct ProbeCtx {
-  std::mutex mu;
-  int ready = 0;
+// Per-device cached probe context (CtxBase, crohost.h): the probe runs on
+// every attach, so allocations and events are created once and reused — only
+// the kernels, copies and compares run per call.
+struct ProbeCtx : CtxBase {
   long long vram_total = 0, vram_free = 0;  // hipMemGetInfo is sysfs-backed
                                             // and ms-scale: snapshot at init
   float *dA = nullptr, *dB = nullptr, *dD = nullptr;
   float4 *src = nullptr, *dst = nullptr;
   float* sink = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
   char gcn_arch[64] = {0};  // hipGetDeviceProperties costs milliseconds —
                             // queried once, the probe runs per attach
 };
-static ProbeCtx g_ctx[64];
+static ProbeCtx g_ctx[kMaxDevices];
 
-constexpr int kCheckK = 64;  // K of the probe's exact f32 check
-constexpr int kBlock = 256;
 constexpr int kBwGrid = 8192;
 constexpr size_t kBwBytes = (size_t)256 << 20;  // each of src and dst
-constexpr int kMaxTileK = 4096;
 constexpr int kGuardVecs = 64;  // cro_probe_copy: vectors after dst, preset to 0xA5
 constexpr unsigned long long kMaxCopyVecs = kBwBytes / sizeof(float4);
 constexpr int kMaxCopyGrid = 1 << 16;
@@ -182,22 +133,22 @@ static void launch_probe_copy(const ProbeCtx* ctx) {
 }
 
 // Caller holds ctx->mu and has made `device` current.
-static int ensure_ctx(ProbeCtx* ctx, int device, struct CroProbeResult* out) {
-  if (ctx->ready) return 0;
-  CHECK(hipMalloc(&ctx->dA, 16 * kCheckK * sizeof(float)));
-  CHECK(hipMalloc(&ctx->dB, kCheckK * 16 * sizeof(float)));
-  CHECK(hipMalloc(&ctx->dD, 256 * sizeof(float)));
-  CHECK(hipMalloc(&ctx->src, kBwBytes));
-  CHECK(hipMalloc(&ctx->dst, kBwBytes));
-  CHECK(hipMemset(ctx->src, 0x5a, kBwBytes));
-  CHECK(hipMalloc(&ctx->sink, 1024 * sizeof(float)));
-  CHECK(hipEventCreate(&ctx->e0));
-  CHECK(hipEventCreate(&ctx->e1));
+static hipError_t ensure_ctx(ProbeCtx* ctx, int device) {
+  if (ctx->ready) return hipSuccess;
+  TRY(hipMalloc(&ctx->dA, 16 * CRO_COV_F32_K * sizeof(float)));
+  TRY(hipMalloc(&ctx->dB, CRO_COV_F32_K * 16 * sizeof(float)));
+  TRY(hipMalloc(&ctx->dD, CRO_COV_F32_ELEMS * sizeof(float)));
+  TRY(hipMalloc(&ctx->src, kBwBytes));
+  TRY(hipMalloc(&ctx->dst, kBwBytes));
+  TRY(hipMemset(ctx->src, 0x5a, kBwBytes));
+  TRY(hipMalloc(&ctx->sink, 1024 * sizeof(float)));
+  TRY(hipEventCreate(&ctx->e0));
+  TRY(hipEventCreate(&ctx->e1));
   hipDeviceProp_t prop;
-  CHECK(hipGetDeviceProperties(&prop, device));
+  TRY(hipGetDeviceProperties(&prop, device));
   snprintf(ctx->gcn_arch, sizeof(ctx->gcn_arch), "%s", prop.gcnArchName);
   size_t free_b = 0, total_b = 0;
-  CHECK(hipMemGetInfo(&free_b, &total_b));
+  TRY(hipMemGetInfo(&free_b, &total_b));
   ctx->vram_total = (long long)total_b;
   ctx->vram_free = (long long)free_b;
   // one warm round at init covers kernel-code upload; per-call warms are
@@ -205,15 +156,9 @@ static int ensure_ctx(ProbeCtx* ctx, int device, struct CroProbeResult* out) {
   launch_probe_copy(ctx);
   hipLaunchKernelGGL(mfma_bf16_rate_kernel<false>, dim3(1024), dim3(256), 0, 0, ctx->sink,
                      64);
-  CHECK(hipDeviceSynchronize());
+  TRY(hipDeviceSynchronize());
   ctx->ready = 1;
-  return 0;
-}
-
-static int bad_opt(struct CroProbeResult* out, const char* what) {
-  snprintf(out->msg, sizeof(out->msg), "bad argument: %s", what);
-  out->ok = 0;
-  return -1;
+  return hipSuccess;
 }
 
 extern "C" int cro_probe_run_opts(int device, const struct CroProbeOpts* opts,
@@ -226,54 +171,36 @@ extern "C" int cro_probe_run_opts(int device, const struct CroProbeOpts* opts,
   memset(&o, 0, sizeof(o));
   if (opts) o = *opts;
   // !(x >= 0) also refuses a NaN
-  if (!(o.hbm_floor_gbps >= 0.0)) return bad_opt(out, "hbm_floor_gbps");
-  if (!(o.bf16_floor_tflops >= 0.0)) return bad_opt(out, "bf16_floor_tflops");
-  if (o.selftest_mode < 0 || o.selftest_mode > 1) return bad_opt(out, "selftest_mode");
-  if (o.selftest_bit < 0 || o.selftest_bit > 31) return bad_opt(out, "selftest_bit");
-  if (o.selftest_elem >= 256) return bad_opt(out, "selftest_elem");
+  if (!(o.hbm_floor_gbps >= 0.0)) return bad_arg(out, "hbm_floor_gbps");
+  if (!(o.bf16_floor_tflops >= 0.0)) return bad_arg(out, "bf16_floor_tflops");
+  if (o.selftest_mode < 0 || o.selftest_mode > 1) return bad_arg(out, "selftest_mode");
+  if (o.selftest_bit < 0 || o.selftest_bit > 31) return bad_arg(out, "selftest_bit");
+  if (o.selftest_elem >= CRO_COV_F32_ELEMS) return bad_arg(out, "selftest_elem");
   const double hbm_floor = o.hbm_floor_gbps > 0.0 ? o.hbm_floor_gbps : 500.0;
   const double bf16_floor = o.bf16_floor_tflops > 0.0 ? o.bf16_floor_tflops : 100.0;
 
-  int count = 0;
-  CHECK(hipGetDeviceCount(&count));
-  if (device < 0 || device >= count) {
-    snprintf(out->msg, sizeof(out->msg), "device %d out of range (%d present)",
-             device, count);
-    return -1;
-  }
-  ProbeCtx* ctx = (device < 64) ? &g_ctx[device] : nullptr;
-  if (ctx == nullptr) {
-    snprintf(out->msg, sizeof(out->msg), "device ordinal %d above cache limit", device);
-    return -1;
-  }
-  std::lock_guard<std::mutex> lock(ctx->mu);
-  CHECK(hipSetDevice(device));
+  std::unique_lock<std::mutex> lock;
+  ProbeCtx* ctx = enter_device(g_ctx, device, lock, out->msg, sizeof(out->msg));
+  if (ctx == nullptr) return -1;
 
   // -- exact f32 MFMA ------------------------------------------------------
+  // inputs and expected tile are the coverage stage's at seed 0 (crocoverage.h)
   out->t_setup_ms = now_ms() - t0;
   t0 = now_ms();
-  const int K = kCheckK;
-  float hA[16 * K], hB[K * 16], hD[256], refD[256];
-  unsigned s = 0x9e3779b9u;
-  for (int i = 0; i < 16 * K; ++i) {
-    s = s * 1664525u + 1013904223u;
-    hA[i] = ((float)(s >> 8) / 16777216.0f) - 0.5f;
-  }
-  for (int i = 0; i < K * 16; ++i) {
-    s = s * 1664525u + 1013904223u;
-    hB[i] = ((float)(s >> 8) / 16777216.0f) - 0.5f;
-  }
-  const size_t bytes = kBwBytes;  // bw buffers (see below)
-  if (ensure_ctx(ctx, device, out) != 0) return -1;
+  float hA[16 * CRO_COV_F32_K], hB[CRO_COV_F32_K * 16];
+  float hD[CRO_COV_F32_ELEMS], refD[CRO_COV_F32_ELEMS];
+  cro_cov_make_f32(0, hA, hB);
+  CHECK(ensure_ctx(ctx, device));
   snprintf(out->gcn_arch, sizeof(out->gcn_arch), "%s", ctx->gcn_arch);
   out->vram_total = ctx->vram_total;
   out->vram_free = ctx->vram_free;
   CHECK(hipMemcpy(ctx->dA, hA, sizeof(hA), hipMemcpyHostToDevice));
   CHECK(hipMemcpy(ctx->dB, hB, sizeof(hB), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(mfma_f32_check_kernel, dim3(1), dim3(64), 0, 0, ctx->dA, ctx->dB, ctx->dD, K);
+  hipLaunchKernelGGL(mfma_f32_check_kernel, dim3(1), dim3(64), 0, 0, ctx->dA, ctx->dB, ctx->dD,
+                     CRO_COV_F32_K);
   CHECK(hipGetLastError());
   CHECK(hipMemcpy(hD, ctx->dD, sizeof(hD), hipMemcpyDeviceToHost));
-  host_mfma_ref(hA, hB, refD, K);
+  cro_cov_ref_f32(hA, hB, refD);
   if (o.selftest_mode == 1) {
     // self-test, for tests only: one bit of one expected element is flipped,
     // so the exact gate must fire on data alone (as coverage.hip's mode 1)
@@ -290,26 +217,23 @@ extern "C" int cro_probe_run_opts(int device, const struct CroProbeOpts* opts,
   // 256 MiB src + dst from the cached context (2 GiB of traffic per
   // measurement — ample signal without putting hipMalloc on the
   // attach-latency path or pinning more of the 288 GB than a gate needs)
-  hipEvent_t e0 = ctx->e0, e1 = ctx->e1;
-  CHECK(hipEventRecord(e0));
   const int reps = 8;
-  for (int i = 0; i < reps; ++i) launch_probe_copy(ctx);
-  CHECK(hipEventRecord(e1));
-  CHECK(hipEventSynchronize(e1));
   float ms = 0.f;
-  CHECK(hipEventElapsedTime(&ms, e0, e1));
-  out->hbm_gbps = (double)(2.0 * bytes * reps) / (ms * 1e6);
+  const auto copies = [&] {
+    for (int i = 0; i < reps; ++i) launch_probe_copy(ctx);
+  };
+  CHECK(timed_ms(*ctx, &ms, copies));
+  out->hbm_gbps = (double)(2.0 * kBwBytes * reps) / (ms * 1e6);
 
   out->t_bw_ms = now_ms() - t0;
   t0 = now_ms();
   // -- bf16 MFMA rate ------------------------------------------------------
   const int blocks = 1024, iters = 2048;
-  CHECK(hipEventRecord(e0));
-  hipLaunchKernelGGL(mfma_bf16_rate_kernel<false>, dim3(blocks), dim3(256), 0, 0, ctx->sink,
-                     iters);
-  CHECK(hipEventRecord(e1));
-  CHECK(hipEventSynchronize(e1));
-  CHECK(hipEventElapsedTime(&ms, e0, e1));
+  const auto bf16_rate = [&] {
+    hipLaunchKernelGGL(mfma_bf16_rate_kernel<false>, dim3(blocks), dim3(256), 0, 0, ctx->sink,
+                       iters);
+  };
+  CHECK(timed_ms(*ctx, &ms, bf16_rate));
   double waves = (double)blocks * 256.0 / 64.0;
   double flops = waves * 4.0 * (double)iters * 2.0 * 32.0 * 32.0 * 16.0;
   out->bf16_tflops = flops / (ms * 1e9);
@@ -351,21 +275,19 @@ extern "C" int cro_probe_mfma_f32(int device, const float* A, const float* B,
   if (K <= 0 || K > kMaxTileK || (K & 3) != 0) return -10;
   const size_t in_bytes = (size_t)16 * K * sizeof(float), out_bytes = 256 * sizeof(float);
   if (hipSetDevice(device) != hipSuccess) return -1;
-  float *dA = nullptr, *dB = nullptr, *dD = nullptr;
-  hipError_t e = hipMalloc(&dA, in_bytes);
-  if (e == hipSuccess) e = hipMalloc(&dB, in_bytes);
-  if (e == hipSuccess) e = hipMalloc(&dD, out_bytes);
-  if (e == hipSuccess) e = hipMemcpy(dA, A, in_bytes, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dB, B, in_bytes, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(mfma_f32_check_kernel, dim3(1), dim3(64), 0, 0, dA, dB, dD, K);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpy(D, dD, out_bytes, hipMemcpyDeviceToHost);
-  if (dA) (void)hipFree(dA);
-  if (dB) (void)hipFree(dB);
-  if (dD) (void)hipFree(dD);
-  return e == hipSuccess ? 0 : -1;
+  DevBuf<float> dA, dB, dD;
+  const auto run = [&]() -> hipError_t {
+    TRY(dA.alloc(in_bytes));
+    TRY(dB.alloc(in_bytes));
+    TRY(dD.alloc(out_bytes));
+    TRY(hipMemcpy(dA.get(), A, in_bytes, hipMemcpyHostToDevice));
+    TRY(hipMemcpy(dB.get(), B, in_bytes, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(mfma_f32_check_kernel, dim3(1), dim3(64), 0, 0, dA.get(), dB.get(),
+                       dD.get(), K);
+    TRY(hipGetLastError());
+    return hipMemcpy(D, dD.get(), out_bytes, hipMemcpyDeviceToHost);
+  };
+  return run() == hipSuccess ? 0 : -1;
 }
 
 // bw_copy_kernel on caller data: n4 16-byte vectors, grid_blocks x 256
@@ -382,29 +304,24 @@ extern "C" int cro_probe_copy(int device, const void* src_host, unsigned long lo
   const size_t bytes = (size_t)n4 * sizeof(float4);
   const size_t guard_bytes = kGuardVecs * sizeof(float4);
   if (hipSetDevice(device) != hipSuccess) return -1;
-  float4 *src = nullptr, *dst = nullptr;
+  DevBuf<float4> src, dst;
   std::vector<unsigned char> back(bytes > guard_bytes ? bytes : guard_bytes);
-  hipError_t e = hipMalloc(&src, bytes);
-  if (e == hipSuccess) e = hipMalloc(&dst, bytes + guard_bytes);
-  if (e == hipSuccess) e = hipMemcpy(src, src_host, bytes, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(dst, 0xA5, bytes + guard_bytes);
-  if (e == hipSuccess) {
-    launch_copy(src, dst, (size_t)n4, grid_blocks);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpy(dst_host, dst, bytes, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(back.data(), dst + n4, guard_bytes, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) {
+  const auto run = [&]() -> hipError_t {
+    TRY(src.alloc(bytes));
+    TRY(dst.alloc(bytes + guard_bytes));
+    TRY(hipMemcpy(src.get(), src_host, bytes, hipMemcpyHostToDevice));
+    TRY(hipMemset(dst.get(), 0xA5, bytes + guard_bytes));
+    launch_copy(src.get(), dst.get(), (size_t)n4, grid_blocks);
+    TRY(hipGetLastError());
+    TRY(hipMemcpy(dst_host, dst.get(), bytes, hipMemcpyDeviceToHost));
+    TRY(hipMemcpy(back.data(), dst.get() + n4, guard_bytes, hipMemcpyDeviceToHost));
     int ok = 1;
     for (size_t i = 0; i < guard_bytes; ++i) ok &= back[i] == 0xA5;
     *guard_ok = ok;
-    e = hipMemcpy(back.data(), src, bytes, hipMemcpyDeviceToHost);
-  }
-  const bool src_same = e == hipSuccess && memcmp(back.data(), src_host, bytes) == 0;
-  if (src) (void)hipFree(src);
-  if (dst) (void)hipFree(dst);
-  if (e != hipSuccess) return -1;
-  return src_same ? 0 : -11;
+    return hipMemcpy(back.data(), src.get(), bytes, hipMemcpyDeviceToHost);
+  };
+  if (run() != hipSuccess) return -1;
+  return memcmp(back.data(), src_host, bytes) == 0 ? 0 : -11;
 }
 
 // The probe's own copy launch, once, on the cached context with dst zeroed
@@ -416,25 +333,23 @@ extern "C" int cro_probe_bw_selfcheck(int device, unsigned long long* n_bad,
   if (n_bad == nullptr || first_bad == nullptr) return -10;
   *n_bad = 0;
   *first_bad = ~0ull;
-  struct CroProbeResult scratch;
-  struct CroProbeResult* out = &scratch;  // reuse CHECK() plumbing
-  memset(out, 0, sizeof(*out));
-  int count = 0;
-  CHECK(hipGetDeviceCount(&count));
-  if (device < 0 || device >= count || device >= 64) return -1;
-  ProbeCtx* ctx = &g_ctx[device];
-  std::lock_guard<std::mutex> lock(ctx->mu);
-  CHECK(hipSetDevice(device));
-  if (ensure_ctx(ctx, device, out) != 0) return -1;
-  CHECK(hipMemset(ctx->dst, 0, kBwBytes));
-  launch_probe_copy(ctx);
-  CHECK(hipGetLastError());
-  CHECK(hipDeviceSynchronize());
+  std::unique_lock<std::mutex> lock;
+  ProbeCtx* ctx = enter_device(g_ctx, device, lock, nullptr, 0);  // rc only, no message
+  if (ctx == nullptr) return -1;
+  const auto copy_once = [&]() -> hipError_t {
+    TRY(ensure_ctx(ctx, device));
+    TRY(hipMemset(ctx->dst, 0, kBwBytes));
+    launch_probe_copy(ctx);
+    TRY(hipGetLastError());
+    return hipDeviceSynchronize();
+  };
+  if (copy_once() != hipSuccess) return -1;
   const size_t chunk = (size_t)32 << 20;
   std::vector<unsigned char> host(chunk);
   for (size_t off = 0; off < kBwBytes; off += chunk) {
-    CHECK(hipMemcpy(host.data(), (const unsigned char*)ctx->dst + off, chunk,
-                    hipMemcpyDeviceToHost));
+    if (hipMemcpy(host.data(), (const unsigned char*)ctx->dst + off, chunk,
+                  hipMemcpyDeviceToHost) != hipSuccess)
+      return -1;
     for (size_t i = 0; i < chunk; i += 8) {
       unsigned long long w;
       memcpy(&w, &host[i], 8);
@@ -460,19 +375,20 @@ extern "C" int cro_probe_bf16_sink(int device, int blocks, int iters, int all_la
   if (iters < 0 || iters > kMaxSinkIters) return -10;
   const size_t bytes = (size_t)blocks * (all_lanes ? kBlock : 1) * sizeof(float);
   if (hipSetDevice(device) != hipSuccess) return -1;
-  float* d = nullptr;
-  hipError_t e = hipMalloc(&d, bytes);
-  if (e == hipSuccess) e = hipMemset(d, 0xFF, bytes);
-  if (e == hipSuccess) {
+  DevBuf<float> d;
+  const auto run = [&]() -> hipError_t {
+    TRY(d.alloc(bytes));
+    TRY(hipMemset(d.get(), 0xFF, bytes));
     if (all_lanes)
-      hipLaunchKernelGGL(mfma_bf16_rate_kernel<true>, dim3(blocks), dim3(kBlock), 0, 0, d, iters);
+      hipLaunchKernelGGL(mfma_bf16_rate_kernel<true>, dim3(blocks), dim3(kBlock), 0, 0, d.get(),
+                         iters);
     else
-      hipLaunchKernelGGL(mfma_bf16_rate_kernel<false>, dim3(blocks), dim3(kBlock), 0, 0, d, iters);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpy(out_host, d, bytes, hipMemcpyDeviceToHost);
-  if (d) (void)hipFree(d);
-  return e == hipSuccess ? 0 : -1;
+      hipLaunchKernelGGL(mfma_bf16_rate_kernel<false>, dim3(blocks), dim3(kBlock), 0, 0, d.get(),
+                         iters);
+    TRY(hipGetLastError());
+    return hipMemcpy(out_host, d.get(), bytes, hipMemcpyDeviceToHost);
+  };
+  return run() == hipSuccess ? 0 : -1;
 }
 
 // Raw VRAM alloc/free for the self-identification fingerprint

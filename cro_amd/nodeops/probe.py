@@ -308,6 +308,26 @@ def _probe_opts(hbm_floor_gbps=0.0, bf16_floor_tflops=0.0, selftest_mode=0, self
     )
 
 
+def _result_dict(res: ctypes.Structure, rc: int) -> dict:
+    """A result struct as the dict the controller and the tests see: ``ok``
+    (gated by rc) and ``rc`` first, then the struct's other fields in order;
+    text decoded, flags as bool, of the bad-CU key slots only those in use,
+    and ``reserved`` dropped."""
+    out = {"ok": bool(res.ok) and rc == 0, "rc": rc}
+    for name, _ in res._fields_:
+        if name in ("ok", "rc", "reserved"):
+            continue
+        value = getattr(res, name)
+        if name == "mfma_f32_exact":
+            value = bool(value)
+        elif name == "bad_cu_keys":
+            value = [int(k) for k in value][: res.n_bad_cu_keys]
+        elif isinstance(value, bytes):
+            value = value.decode(errors="replace")
+        out[name] = value
+    return out
+
+
 def run_probe(device: int = 0, **opts) -> dict:
     """Quick probe.  Options as ``struct CroProbeOpts``; zero takes the library
     default (floors of 500 GB/s and 100 TF).  The ``selftest_*`` options are
@@ -319,21 +339,7 @@ def run_probe(device: int = 0, **opts) -> dict:
         rc = lib.cro_probe_run_opts(device, ctypes.byref(c_opts), ctypes.byref(res))
     else:
         rc = lib.cro_probe_run(device, ctypes.byref(res))
-    return {
-        "ok": bool(res.ok) and rc == 0,
-        "rc": rc,
-        "mfma_f32_exact": bool(res.mfma_f32_exact),
-        "hbm_gbps": res.hbm_gbps,
-        "bf16_tflops": res.bf16_tflops,
-        "vram_total": res.vram_total,
-        "vram_free": res.vram_free,
-        "t_setup_ms": res.t_setup_ms,
-        "t_mfma_ms": res.t_mfma_ms,
-        "t_bw_ms": res.t_bw_ms,
-        "t_bf16_ms": res.t_bf16_ms,
-        "gcn_arch": res.gcn_arch.decode(errors="replace"),
-        "msg": res.msg.decode(errors="replace"),
-    }
+    return _result_dict(res, rc)
 
 
 def probe_fn_for_nodeops(gpu) -> dict:
@@ -496,11 +502,7 @@ def run_integrity(
     )
     res = CroIntegrityResult()
     rc = lib.cro_probe_integrity(device, ctypes.byref(opts), ctypes.byref(res))
-    out = {"ok": bool(res.ok) and rc == 0, "rc": rc}
-    for name, _ in CroIntegrityResult._fields_[2:]:
-        value = getattr(res, name)
-        out[name] = value.decode(errors="replace") if isinstance(value, bytes) else value
-    return out
+    return _result_dict(res, rc)
 
 
 def pattern_words(base_word: int, n_words: int, seed: int, invert):
@@ -556,19 +558,6 @@ def pattern_verify(device: int, seed: int, invert, base_word: int, words) -> dic
 # -- compute-coverage stage (cro_amd/hip/coverage.hip) ----------------------------
 
 
-def _compute_dict(res: "CroComputeResult", rc: int) -> dict:
-    out = {"ok": bool(res.ok) and rc == 0, "rc": rc}
-    for name, _ in CroComputeResult._fields_[2:]:
-        value = getattr(res, name)
-        if name == "bad_cu_keys":
-            value = [int(k) for k in value][: res.n_bad_cu_keys]
-        elif isinstance(value, bytes):
-            value = value.decode(errors="replace")
-        out[name] = value
-    del out["reserved"]
-    return out
-
-
 def _compute_opts(grid_blocks=0, lds_bytes=0, iters=0, max_rounds=0, seed=0,
                   min_cu_fraction=0.0, selftest_mode=0, selftest_test=0, selftest_elem=0,
                   selftest_bit=0, selftest_key=0) -> "CroComputeOpts":
@@ -594,7 +583,7 @@ def run_compute(device: int = 0, **opts) -> dict:
     c_opts = _compute_opts(**opts)
     res = CroComputeResult()
     rc = lib.cro_probe_compute(device, ctypes.byref(c_opts), ctypes.byref(res))
-    return _compute_dict(res, rc)
+    return _result_dict(res, rc)
 
 
 def run_compute_records(device: int = 0, **opts):
@@ -612,7 +601,7 @@ def run_compute_records(device: int = 0, **opts):
     cap = max(blocks * 4 * rounds, 1)
     buf = (CroCoverageRecord * cap)()
     rc = lib.cro_probe_compute_records(device, ctypes.byref(c_opts), ctypes.byref(res), buf, cap)
-    out = _compute_dict(res, rc)
+    out = _result_dict(res, rc)
     n = min(out["rounds"] * out["grid_blocks"] * 4, cap)
     dtype = np.dtype([(name, np.uint32) for name, _ in CroCoverageRecord._fields_])
     records = np.frombuffer(buf, dtype=dtype, count=cap)[:n].copy()

@@ -325,6 +325,19 @@ def test_f32_inputs_are_the_quick_probes():
     assert np.array_equal(np.concatenate([a.ravel(), b.ravel()]), np.array(vals, np.float32))
 
 
+def test_quick_probes_documented_inputs_are_the_headers_at_seed_0():
+    """The quick probe takes its inputs from cro_cov_make_f32(0): the inputs the
+    benchmark documents for it are bit for bit what compute_inputs(0) mirrors
+    (and test_inputs_and_expected_tiles_match_header ties that to the header)."""
+    import bench
+
+    a, b = bench._probe_inputs()
+    a0, b0 = probe_mod.compute_inputs(0)["f32"]
+    for got, want in ((a, a0), (b, b0)):
+        assert got.dtype == want.dtype == np.float32 and got.shape == want.shape
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+
+
 @pytest.mark.parametrize("seed", [0, 7])
 def test_expected_tiles_are_plain_integer_matmuls(seed):
     inputs = probe_mod.compute_inputs(seed)
@@ -744,14 +757,14 @@ def test_build_goes_stale_on_coverage_source_or_header(tmp_path, monkeypatch):
 
     names = {os.path.basename(p) for p in hip_build.ALL_SRCS + hip_build.ALL_HEADERS}
     assert names == {"probe.hip", "integrity.hip", "coverage.hip", "croprobe.h",
-                     "cropattern.h", "crocoverage.h"}
+                     "cropattern.h", "crocoverage.h", "crohost.h", "cromfma.h"}
     assert all(os.path.exists(p) for p in hip_build.ALL_SRCS + hip_build.ALL_HEADERS)
     # build() and build_agent() look at the new files: stand-ins with chosen
     # mtimes, a hipcc that only records its command line
     lib, agent = tmp_path / "libcroprobe.so", tmp_path / "croagent"
     files = {}
     for name in ("probe.hip", "integrity.hip", "coverage.hip", "croprobe.h", "cropattern.h",
-                 "crocoverage.h", "croagent.cpp"):
+                 "crocoverage.h", "crohost.h", "cromfma.h", "croagent.cpp"):
         files[name] = tmp_path / name
         files[name].write_text("")
         os.utime(files[name], (100, 100))
@@ -765,7 +778,9 @@ def test_build_goes_stale_on_coverage_source_or_header(tmp_path, monkeypatch):
     monkeypatch.setattr(hip_build, "COVERAGE_SRC", str(files["coverage.hip"]))
     monkeypatch.setattr(hip_build, "COVERAGE_HEADER", str(files["crocoverage.h"]))
     monkeypatch.setattr(hip_build, "ALL_SRCS", srcs + [str(files["coverage.hip"])])
-    monkeypatch.setattr(hip_build, "ALL_HEADERS", hdrs + [str(files["crocoverage.h"])])
+    internal = [str(files[n]) for n in ("crohost.h", "cromfma.h")]
+    monkeypatch.setattr(hip_build, "INTERNAL_HEADERS", internal)
+    monkeypatch.setattr(hip_build, "ALL_HEADERS", hdrs + [str(files["crocoverage.h"])] + internal)
     monkeypatch.setattr(hip_build, "OUT", str(lib))
     monkeypatch.setattr(hip_build, "AGENT_SRC", str(files["croagent.cpp"]))
     monkeypatch.setattr(hip_build, "AGENT_OUT", str(agent))
@@ -779,7 +794,8 @@ def test_build_goes_stale_on_coverage_source_or_header(tmp_path, monkeypatch):
     monkeypatch.setattr(hip_build.subprocess, "run", fake_run)
     hip_build.build()
     assert commands == []  # everything up to date
-    for newer, want_lib in (("coverage.hip", True), ("crocoverage.h", True)):
+    for newer, want_lib in (("coverage.hip", True), ("crocoverage.h", True),
+                            ("crohost.h", True), ("cromfma.h", True)):
         for out in (lib, agent):
             os.utime(out, (200, 200))
         os.utime(files[newer], (300, 300))

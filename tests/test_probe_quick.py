@@ -418,6 +418,19 @@ class FakeLib:
         res._obj.hbm_gbps = 4321.0
         return self.rc
 
+    def cro_probe_integrity(self, device, opts, res):
+        res._obj.ok = 1
+        res._obj.failed_stage = b"vram"
+        return self.rc
+
+    def cro_probe_compute(self, device, opts, res):
+        res._obj.ok = 1
+        res._obj.n_bad_cu_keys = 2
+        res._obj.bad_cu_keys[0], res._obj.bad_cu_keys[1], res._obj.bad_cu_keys[2] = 5, 6, 7
+        res._obj.reserved = 9
+        res._obj.failed_test = b"lds"
+        return self.rc
+
 
 def test_run_probe_forwards_the_options(monkeypatch):
     fake = FakeLib()
@@ -437,6 +450,52 @@ def test_run_probe_forwards_the_options(monkeypatch):
         probe_mod.run_probe(0, hbm_floor=1.0)
     fake.rc = -3
     assert probe_mod.run_probe(0, hbm_floor_gbps=1e9)["ok"] is False  # rc gates ok
+
+
+QUICK_KEYS = [
+    "ok", "rc", "mfma_f32_exact", "hbm_gbps", "bf16_tflops", "vram_total", "vram_free",
+    "t_setup_ms", "t_mfma_ms", "t_bw_ms", "t_bf16_ms", "gcn_arch", "msg",
+]
+INTEGRITY_KEYS = [
+    "ok", "rc", "n_bad", "first_bad_byte", "bits_bad", "vram_passes", "link_passes",
+    "vram_chunks", "vram_bytes_verified", "h2d_dma_bytes_verified", "d2h_dma_bytes_verified",
+    "h2d_kernel_bytes_verified", "d2h_kernel_bytes_verified", "vram_n_bad", "h2d_dma_n_bad",
+    "d2h_dma_n_bad", "h2d_kernel_n_bad", "d2h_kernel_n_bad", "vram_fill_gbps",
+    "vram_verify_gbps", "h2d_dma_gbps", "d2h_dma_gbps", "h2d_kernel_gbps", "d2h_kernel_gbps",
+    "t_vram_ms", "t_link_dma_ms", "t_link_kernel_ms", "t_total_ms", "failed_stage", "msg",
+]
+COMPUTE_KEYS = [
+    "ok", "rc", "cus_expected", "rounds", "waves_run", "waves_bad", "bad_f32", "bad_i8",
+    "bad_bf16", "bad_lds", "first_bad_index", "cus_seen", "xcds_seen", "simds_seen", "cus_bad",
+    "xcd", "se", "sh", "cu", "simd", "first_fail_mask", "n_bad", "first_bad", "bits_bad",
+    "n_bad_cu_keys", "bad_cu_keys", "first_bad_round", "first_bad_record", "grid_blocks",
+    "lds_bytes", "iters", "gpu_ms", "t_total_ms", "failed_test", "msg",
+]
+
+
+def test_result_dicts_keep_their_keys_order_and_types(monkeypatch):
+    """What run_probe, run_integrity and run_compute hand to the controller and
+    what croagent prints share these shapes: the keys in this order, booleans
+    where the struct holds a flag, text decoded, and of the compute result's
+    eight key slots only the ones in use."""
+    monkeypatch.setattr(probe_mod, "_lib", FakeLib(rc=-7))
+    quick = probe_mod.run_probe(0)
+    integrity = probe_mod.run_integrity(0)
+    compute = probe_mod.run_compute(0)
+    assert list(quick) == QUICK_KEYS
+    assert list(integrity) == INTEGRITY_KEYS
+    assert list(compute) == COMPUTE_KEYS  # no "reserved"
+    for got in (quick, integrity, compute):
+        assert got["ok"] is False and got["rc"] == -7  # ok in the struct, but rc gates it
+        assert isinstance(got["msg"], str)
+        for key, value in got.items():
+            assert not isinstance(value, bytes), key
+    assert quick["mfma_f32_exact"] is False and quick["msg"] == "ok" and quick["gcn_arch"] == ""
+    assert type(quick["hbm_gbps"]) is float and type(quick["vram_total"]) is int
+    assert integrity["failed_stage"] == "vram" and type(integrity["n_bad"]) is int
+    assert compute["bad_cu_keys"] == [5, 6] and compute["n_bad_cu_keys"] == 2
+    assert all(type(k) is int for k in compute["bad_cu_keys"])
+    assert compute["failed_test"] == "lds" and type(compute["gpu_ms"]) is float
 
 
 def test_probe_hooks_untouched(monkeypatch):
