@@ -277,9 +277,9 @@ int resolve_device_by_bdf(const std::string& bdf) {
 
 void print_integrity(const CroIntegrityResult& r) {
   printf("\"integrity\":{\"ok\":%s,\"rc\":%d,\"n_bad\":%llu,\"first_bad_byte\":%llu,"
-         "\"bits_bad\":%u,\"failed_stage\":\"%s\",\"vram_passes\":%d,\"link_passes\":%d,"
-         "\"vram_chunks\":%d,",
-         r.ok ? "true" : "false", r.rc, r.n_bad, r.first_bad_byte, r.bits_bad,
+         "\"bits_bad\":%u,\"first_bad_got\":%u,\"failed_stage\":\"%s\",\"vram_passes\":%d,"
+         "\"link_passes\":%d,\"vram_chunks\":%d,",
+         r.ok ? "true" : "false", r.rc, r.n_bad, r.first_bad_byte, r.bits_bad, r.first_bad_got,
          r.failed_stage, r.vram_passes, r.link_passes, r.vram_chunks);
   printf("\"vram_bytes_verified\":%lld,\"h2d_dma_bytes_verified\":%lld,"
          "\"d2h_dma_bytes_verified\":%lld,\"h2d_kernel_bytes_verified\":%lld,"

@@ -26,8 +26,11 @@ COVERAGE_HEADER = os.path.join(HIP_DIR, "crocoverage.h")
 # what the three sources share and nothing else includes: host plumbing and
 # the wave-level matrix code
 INTERNAL_HEADERS = [os.path.join(HIP_DIR, "crohost.h"), os.path.join(HIP_DIR, "cromfma.h")]
+# the deep probe's host-only pieces (integrity.hip includes it; listed apart
+# for the same reason)
+INTEGRITY_HEADER = os.path.join(HIP_DIR, "crointegrity.h")
 ALL_SRCS = SRCS + [COVERAGE_SRC]
-ALL_HEADERS = HEADERS + [COVERAGE_HEADER] + INTERNAL_HEADERS
+ALL_HEADERS = HEADERS + [COVERAGE_HEADER, INTEGRITY_HEADER] + INTERNAL_HEADERS
 OUT = os.path.join(HIP_DIR, "libcroprobe.so")
 AGENT_SRC = os.path.join(AGENT_DIR, "croagent.cpp")
 AGENT_OUT = os.path.join(AGENT_DIR, "croagent")

@@ -1,6 +1,7 @@
 // Shared C ABI for the gfx950 health probe library (libcroprobe.so).
 // Consumers: probe.hip, integrity.hip and coverage.hip (implementation; their
-// shared internals are in crohost.h and cromfma.h, which nothing else includes),
+// shared internals are in crohost.h and cromfma.h, which nothing else includes;
+// integrity.hip's host-only pieces are in crointegrity.h),
 // agent/croagent.cpp (native CLI),
 // nodeops/probe.py (ctypes — keep CroProbeResult field order in sync there).
 #pragma once
@@ -71,8 +72,16 @@ struct CroIntegrityOpts {
   long long link_bytes;    // 0 → library default (256 MiB)
   long long chunk_bytes;   // VRAM allocation unit; 0 or > 1 GiB → 1 GiB
   unsigned int seed;       // 0 is a valid seed
-  int reserved;
+  // Self-test, for tests only (all zero = off): in stage selftest_stage (1 vram,
+  // 2 h2d_dma, 3 d2h_dma, 4 h2d_kernel, 5 d2h_kernel) the host flips bit
+  // selftest_bit of word selftest_word of the stage's span after the stage's
+  // data is written and before it is verified, so the stage must detect,
+  // locate and report through data alone.  Every access is in bounds.
+  int selftest_stage;
   double link_floor_gbps;  // 0 = off; else every link rate must reach it
+  int selftest_pass;       // vram only: 0 the pattern pass, 1 the complement pass
+  int selftest_bit;        // 0..31
+  unsigned long long selftest_word;  // below the stage's span in words
 };
 
 struct CroIntegrityResult {
@@ -108,15 +117,20 @@ struct CroIntegrityResult {
   double t_total_ms;
   char failed_stage[32];  // "", "vram", "h2d_dma", "d2h_dma", "h2d_kernel", "d2h_kernel"
   char msg[256];
+  unsigned int first_bad_got;  // the word found at first_bad_byte; 0 when none
+  int reserved;
 };
 
 int cro_probe_integrity(int device, const struct CroIntegrityOpts* opts,
                         struct CroIntegrityResult* out);
 // Raw kernel entries for tests: fill on the device and copy back / upload a
-// host buffer and verify it on the device.
+// host buffer and verify it on the device.  The device buffer is followed by
+// 64 guard vectors; they and the 0-3 slack words after n_words are preset to
+// 0xA5 bytes.  *guard_ok = the fill left all of them untouched; a verify that
+// read one of them would report a mismatch.
 int cro_probe_pattern_fill(int device, unsigned int seed, int invert,
                            unsigned long long base_word, unsigned long long n_words,
-                           unsigned int* host_out);
+                           unsigned int* host_out, int* guard_ok);
 int cro_probe_pattern_verify(int device, unsigned int seed, int invert,
                              unsigned long long base_word, unsigned long long n_words,
                              const unsigned int* host_in, unsigned long long* n_bad,

@@ -16,6 +16,10 @@
 // pointers.  Gates are on data (any mismatch or HIP error fails); rates are
 // reported, and gated only by the optional link_floor_gbps.
 //
+// Everything of this stage that needs no HIP (the host side of the link
+// stages, the sizes, the chunk plan, each stage's seed and polarity) is in
+// crointegrity.h, which the CPU tests compile on their own.
+//
 // Compiled with probe.hip and coverage.hip into libcroprobe.so
 // (cro_amd/hip/build.py); host plumbing shared with them in crohost.h.
 
@@ -24,19 +28,15 @@
 #include <vector>
 
 #include "crohost.h"
+#include "crointegrity.h"
 #include "cropattern.h"
 #include "croprobe.h"
 
 namespace {
 
-struct PatternReport {
-  unsigned long long n_bad;
-  unsigned long long first_bad;  // global word index, all-ones = none
-  unsigned int bits_bad;
-  unsigned int pad;
-};
+using namespace crointegrity;  // PatternReport, host side, sizes, plan, stages
 
-// 1024 workgroups x 256 lanes x 16 B = 16 MiB (2^20 vectors) per grid pass:
+// 1024 workgroups x 256 lanes x 16 B = 4 MiB (2^18 vectors) per grid pass:
 // 4 workgroups on each of the 256 CUs, grid-stride for the rest.
 constexpr unsigned kMaxGrid = 1024;
 
@@ -147,24 +147,6 @@ void launch_verify(const uint32_t* src, uint64_t n_words, uint64_t base_word,
                      src, n_words, base_word, seed, invert, report);
 }
 
-void host_fill(uint32_t* dst, uint64_t n_words, uint32_t seed, uint32_t invert) {
-  for (uint64_t w = 0; w < n_words; ++w) dst[w] = cro_pattern_word(w, seed, invert);
-}
-
-PatternReport host_verify(const uint32_t* src, uint64_t n_words, uint32_t seed,
-                          uint32_t invert) {
-  PatternReport r = {0, ~0ull, 0, 0};
-  for (uint64_t w = 0; w < n_words; ++w) {
-    const uint32_t d = src[w] ^ cro_pattern_word(w, seed, invert);
-    if (d) {
-      if (r.n_bad == 0) r.first_bad = w;
-      ++r.n_bad;
-      r.bits_bad |= d;
-    }
-  }
-  return r;
-}
-
 const PatternReport kCleanReport = {0, ~0ull, 0, 0};
 
 // Per-device cached context (CtxBase, crohost.h): the pinned link buffer, the
@@ -177,12 +159,31 @@ struct IntegCtx : CtxBase {
 };
 IntegCtx g_ictx[kMaxDevices];
 
-int fail_data(CroIntegrityResult* out, const char* stage, const PatternReport& r,
-              unsigned long long stage_base_word) {
+// One word of a still-resident device buffer, for the report of a mismatch;
+// 0 when the copy fails (the mismatch is what the caller reports either way).
+uint32_t device_word(const uint32_t* p) {
+  uint32_t got = 0;
+  if (hipMemcpy(&got, p, sizeof(got), hipMemcpyDeviceToHost) != hipSuccess) got = 0;
+  return got;
+}
+
+// Self-test: flips one bit of one word of device memory from the host.
+hipError_t flip_device_bit(uint32_t* p, int bit) {
+  uint32_t word = 0;
+  TRY(hipMemcpy(&word, p, sizeof(word), hipMemcpyDeviceToHost));
+  word ^= 1u << bit;
+  return hipMemcpy(p, &word, sizeof(word), hipMemcpyHostToDevice);
+}
+
+// `got` is the word found at r.first_bad.
+int fail_data(CroIntegrityResult* out, Stage which, const PatternReport& r,
+              unsigned long long stage_base_word, uint32_t got) {
+  const char* stage = kStages[which].name;
   out->ok = 0;
   out->n_bad = r.n_bad;
   out->first_bad_byte = (r.first_bad - stage_base_word) * 4ull;
   out->bits_bad = r.bits_bad;
+  out->first_bad_got = got;
   snprintf(out->failed_stage, sizeof(out->failed_stage), "%s", stage);
   snprintf(out->msg, sizeof(out->msg),
            "data mismatch in stage %s: %llu bad words, first at byte %llu, bits 0x%08x",
@@ -193,20 +194,21 @@ int fail_data(CroIntegrityResult* out, const char* stage, const PatternReport& r
 double gbps(double bytes, float ms) { return ms > 0.f ? bytes / (ms * 1e6) : 0.0; }
 
 int run_integrity(int device, const CroIntegrityOpts* opts, CroIntegrityResult* out) {
-  const long long kGiB = 1ll << 30;
-  long long vram_bytes = opts && opts->vram_bytes > 0 ? opts->vram_bytes : kGiB;
-  long long link_bytes = opts && opts->link_bytes > 0 ? opts->link_bytes : (256ll << 20);
-  long long chunk_bytes = opts && opts->chunk_bytes > 0 ? opts->chunk_bytes : kGiB;
-  if (chunk_bytes > kGiB) chunk_bytes = kGiB;
-  chunk_bytes &= ~15ll;  // every chunk but the last holds whole 16-byte vectors
-  if (chunk_bytes < 16) chunk_bytes = 16;
-  const uint32_t seed = opts ? opts->seed : 0u;
-  const uint32_t seed_back = seed ^ 0xA5A5A5A5u;  // device→host direction: a stale
-                                                  // host→device image can never pass
-  const double floor_gbps = opts ? opts->link_floor_gbps : 0.0;
-  const uint64_t vram_words = (uint64_t)vram_bytes >> 2;  // whole words only
-  const uint64_t link_words = (uint64_t)link_bytes >> 2;
-  const uint64_t chunk_words = (uint64_t)chunk_bytes >> 2;
+  CroIntegrityOpts o;
+  memset(&o, 0, sizeof(o));
+  if (opts) o = *opts;
+  const Sizes sizes = normalise_sizes(o.vram_bytes, o.link_bytes, o.chunk_bytes);
+  const uint64_t vram_words = sizes.vram_words;
+  const uint64_t link_words = sizes.link_words;
+  const ChunkPlan plan = chunk_plan(vram_words, sizes.chunk_words);
+  const uint32_t seed = o.seed;
+  const double floor_gbps = o.link_floor_gbps;
+  // Self-test, for tests only: in stage `flip_stage` (-1 = off) the host flips
+  // one bit of one word between the stage's write and its compare, so the
+  // stage must detect, locate and report through data alone.
+  const int flip_stage = o.selftest_stage - 1;
+  const int flip_bit = o.selftest_bit;
+  const uint64_t flip_word = o.selftest_word;
 
   std::unique_lock<std::mutex> lock;
   IntegCtx* ctx = enter_device(g_ictx, device, lock, out->msg, sizeof(out->msg));
@@ -216,6 +218,19 @@ int run_integrity(int device, const CroIntegrityOpts* opts, CroIntegrityResult* 
     snprintf(out->msg, sizeof(out->msg), "vram_bytes and link_bytes must be >= 4");
     return -1;
   }
+  if (!(floor_gbps >= 0.0)) return bad_arg(out, "link_floor_gbps");  // refuses a NaN too
+  if (o.selftest_stage < 0 || o.selftest_stage > kNumStages)
+    return bad_arg(out, "selftest_stage");
+  if (flip_bit < 0 || flip_bit > 31) return bad_arg(out, "selftest_bit");
+  if (o.selftest_pass < 0 || o.selftest_pass > 1 || (o.selftest_pass && flip_stage != kVram))
+    return bad_arg(out, "selftest_pass");
+  if (flip_stage >= 0 && flip_word >= stage_span_words(flip_stage, sizes))
+    return bad_arg(out, "selftest_word");
+  // the pinned buffer of a link stage under self-test, after the stage's data
+  // is in it and before the compare
+  const auto flip_pinned = [&](Stage stage) {
+    if (flip_stage == stage) ctx->pinned[flip_word] ^= 1u << flip_bit;
+  };
   if (!ctx->ready) {
     CHECK(hipEventCreate(&ctx->e0));
     CHECK(hipEventCreate(&ctx->e1));
@@ -248,43 +263,44 @@ int run_integrity(int device, const CroIntegrityOpts* opts, CroIntegrityResult* 
 
   // -- VRAM ------------------------------------------------------------------
   double t0 = now_ms();
-  std::vector<uint64_t> chunk_n;
-  for (uint64_t done = 0; done < vram_words;) {
-    const uint64_t n = vram_words - done < chunk_words ? vram_words - done : chunk_words;
+  for (uint64_t c = 0; c < plan.count(); ++c) {
     chunks.emplace_back();
-    CHECK(chunks.back().alloc((n * 4 + 15) & ~15ull));
-    chunk_n.push_back(n);
-    done += n;
+    CHECK(chunks.back().alloc((plan.words(c) * 4 + 15) & ~15ull));
   }
   out->vram_chunks = (int)chunks.size();
+  // word `w` of the span, in the chunk that holds it
+  const auto vram_word = [&](uint64_t w) {
+    const ChunkPos pos = locate(plan, w);
+    return chunks[pos.chunk].get() + pos.word;
+  };
   float fill_ms = 0.f, verify_ms = 0.f;
-  for (uint32_t invert = 0; invert < 2; ++invert) {
+  for (uint32_t pass = 0; pass < 2; ++pass) {
+    const StagePattern pat = stage_pattern(kVram, pass, seed);
     // every chunk in one timed window, at its place in the span's word count
     const auto fill_all = [&] {
-      uint64_t base = 0;
-      for (size_t c = 0; c < chunks.size(); ++c) {
-        launch_fill(chunks[c].get(), chunk_n[c], base, seed, invert);
-        base += chunk_n[c];
-      }
+      for (size_t c = 0; c < chunks.size(); ++c)
+        launch_fill(chunks[c].get(), plan.words(c), plan.base(c), pat.seed, pat.invert);
     };
     const auto verify_all = [&] {
-      uint64_t base = 0;
-      for (size_t c = 0; c < chunks.size(); ++c) {
-        launch_verify(chunks[c].get(), chunk_n[c], base, seed, invert, ctx->d_report);
-        base += chunk_n[c];
-      }
+      for (size_t c = 0; c < chunks.size(); ++c)
+        launch_verify(chunks[c].get(), plan.words(c), plan.base(c), pat.seed, pat.invert,
+                      ctx->d_report);
     };
-    CHECK(timed_ms(*ctx, &ms, fill_all));
+    CHECK(timed_ms(*ctx, &ms, fill_all));  // synchronised when it returns
     fill_ms += ms;
+    if (flip_stage == kVram && (uint32_t)o.selftest_pass == pass)
+      CHECK(flip_device_bit(vram_word(flip_word), flip_bit));
 
     CHECK(hipMemcpy(ctx->d_report, &kCleanReport, sizeof(rep), hipMemcpyHostToDevice));
     CHECK(timed_ms(*ctx, &ms, verify_all));
     verify_ms += ms;
     CHECK(hipMemcpy(&rep, ctx->d_report, sizeof(rep), hipMemcpyDeviceToHost));
-    out->vram_passes = (int)invert + 1;
+    out->vram_passes = (int)pass + 1;
     out->vram_bytes_verified += (long long)(vram_words * 4);
     out->vram_n_bad += rep.n_bad;
-    if (rep.n_bad) return fail_data(out, "vram", rep, 0);
+    if (rep.n_bad)
+      return fail_data(out, kVram, rep, 0,
+                       rep.first_bad < vram_words ? device_word(vram_word(rep.first_bad)) : 0u);
   }
   out->vram_fill_gbps = gbps(2.0 * vram_words * 4, fill_ms);
   out->vram_verify_gbps = gbps(2.0 * vram_words * 4, verify_ms);
@@ -297,22 +313,27 @@ int run_integrity(int device, const CroIntegrityOpts* opts, CroIntegrityResult* 
   t0 = now_ms();
   const double lbytes = (double)(link_words * 4);
   CHECK(dlink.alloc((link_words * 4 + 15) & ~15ull));
-  host_fill(ctx->pinned, link_words, seed, 0);
+  StagePattern pat = stage_pattern(kH2dDma, 0, seed);
+  host_fill(ctx->pinned, link_words, pat.seed, pat.invert);
   const auto h2d_copy = [&] {
     (void)hipMemcpy(dlink.get(), ctx->pinned, link_words * 4, hipMemcpyHostToDevice);
   };
   CHECK(timed_ms(*ctx, &ms, h2d_copy));
   out->h2d_dma_gbps = gbps(lbytes, ms);
+  if (flip_stage == kH2dDma) CHECK(flip_device_bit(dlink.get() + flip_word, flip_bit));
   CHECK(hipMemcpy(ctx->d_report, &kCleanReport, sizeof(rep), hipMemcpyHostToDevice));
-  launch_verify(dlink.get(), link_words, 0, seed, 0, ctx->d_report);
+  launch_verify(dlink.get(), link_words, 0, pat.seed, pat.invert, ctx->d_report);
   CHECK(hipGetLastError());
   CHECK(hipMemcpy(&rep, ctx->d_report, sizeof(rep), hipMemcpyDeviceToHost));
   out->link_passes = 1;
   out->h2d_dma_bytes_verified = (long long)(link_words * 4);
   out->h2d_dma_n_bad = rep.n_bad;
-  if (rep.n_bad) return fail_data(out, "h2d_dma", rep, 0);
+  if (rep.n_bad)
+    return fail_data(out, kH2dDma, rep, 0,
+                     rep.first_bad < link_words ? device_word(dlink.get() + rep.first_bad) : 0u);
 
-  launch_fill(dlink.get(), link_words, 0, seed_back, 0);
+  pat = stage_pattern(kD2hDma, 0, seed);
+  launch_fill(dlink.get(), link_words, 0, pat.seed, pat.invert);
   CHECK(hipGetLastError());
   CHECK(hipDeviceSynchronize());
   const auto d2h_copy = [&] {
@@ -320,35 +341,44 @@ int run_integrity(int device, const CroIntegrityOpts* opts, CroIntegrityResult* 
   };
   CHECK(timed_ms(*ctx, &ms, d2h_copy));
   out->d2h_dma_gbps = gbps(lbytes, ms);
-  rep = host_verify(ctx->pinned, link_words, seed_back, 0);
+  flip_pinned(kD2hDma);
+  rep = host_verify(ctx->pinned, link_words, pat.seed, pat.invert);
   out->d2h_dma_bytes_verified = (long long)(link_words * 4);
   out->d2h_dma_n_bad = rep.n_bad;
-  if (rep.n_bad) return fail_data(out, "d2h_dma", rep, 0);
+  if (rep.n_bad) return fail_data(out, kD2hDma, rep, 0, ctx->pinned[rep.first_bad]);
   CHECK(dlink.free());
   out->t_link_dma_ms = now_ms() - t0;
 
   // -- link, shader loads and stores (complement pattern) ----------------------
   t0 = now_ms();
-  host_fill(ctx->pinned, link_words, seed, 1);
+  pat = stage_pattern(kH2dKernel, 0, seed);
+  host_fill(ctx->pinned, link_words, pat.seed, pat.invert);
+  flip_pinned(kH2dKernel);
   CHECK(hipMemcpy(ctx->d_report, &kCleanReport, sizeof(rep), hipMemcpyHostToDevice));
   const auto h2d_verify = [&] {
-    launch_verify(ctx->pinned_dev, link_words, 0, seed, 1, ctx->d_report);
+    launch_verify(ctx->pinned_dev, link_words, 0, pat.seed, pat.invert, ctx->d_report);
   };
   CHECK(timed_ms(*ctx, &ms, h2d_verify));
   out->h2d_kernel_gbps = gbps(lbytes, ms);
   CHECK(hipMemcpy(&rep, ctx->d_report, sizeof(rep), hipMemcpyDeviceToHost));
   out->h2d_kernel_bytes_verified = (long long)(link_words * 4);
   out->h2d_kernel_n_bad = rep.n_bad;
-  if (rep.n_bad) return fail_data(out, "h2d_kernel", rep, 0);
+  if (rep.n_bad)
+    return fail_data(out, kH2dKernel, rep, 0,
+                     rep.first_bad < link_words ? ctx->pinned[rep.first_bad] : 0u);
 
-  const auto d2h_fill = [&] { launch_fill(ctx->pinned_dev, link_words, 0, seed_back, 1); };
+  pat = stage_pattern(kD2hKernel, 0, seed);
+  const auto d2h_fill = [&] {
+    launch_fill(ctx->pinned_dev, link_words, 0, pat.seed, pat.invert);
+  };
   CHECK(timed_ms(*ctx, &ms, d2h_fill));
   out->d2h_kernel_gbps = gbps(lbytes, ms);
   CHECK(hipDeviceSynchronize());
-  rep = host_verify(ctx->pinned, link_words, seed_back, 1);
+  flip_pinned(kD2hKernel);
+  rep = host_verify(ctx->pinned, link_words, pat.seed, pat.invert);
   out->d2h_kernel_bytes_verified = (long long)(link_words * 4);
   out->d2h_kernel_n_bad = rep.n_bad;
-  if (rep.n_bad) return fail_data(out, "d2h_kernel", rep, 0);
+  if (rep.n_bad) return fail_data(out, kD2hKernel, rep, 0, ctx->pinned[rep.first_bad]);
   out->t_link_kernel_ms = now_ms() - t0;
 
   if (floor_gbps > 0.0) {
@@ -370,6 +400,17 @@ int run_integrity(int device, const CroIntegrityOpts* opts, CroIntegrityResult* 
   return 0;
 }
 
+// Raw entries: the buffer is rounded up to whole vectors and followed by a
+// guard band, all preset to 0xA5 bytes, so a store or a load past n_words
+// shows in data (tests/test_probe_integrity.py: 0xA5A5A5A5 is the pattern at
+// none of those indices).
+constexpr size_t kGuardBytes = 64 * 16;
+constexpr unsigned char kGuardByte = 0xA5;
+
+size_t raw_alloc_bytes(unsigned long long n_words) {
+  return (size_t)((n_words * 4 + 15) & ~15ull) + kGuardBytes;
+}
+
 }  // namespace
 
 extern "C" int cro_probe_integrity(int device, const struct CroIntegrityOpts* opts,
@@ -384,14 +425,28 @@ extern "C" int cro_probe_integrity(int device, const struct CroIntegrityOpts* op
 
 extern "C" int cro_probe_pattern_fill(int device, unsigned int seed, int invert,
                                       unsigned long long base_word,
-                                      unsigned long long n_words, unsigned int* host_out) {
-  if (n_words == 0 || host_out == nullptr) return -10;
+                                      unsigned long long n_words, unsigned int* host_out,
+                                      int* guard_ok) {
+  if (n_words == 0 || host_out == nullptr || guard_ok == nullptr) return -10;
+  *guard_ok = 0;
   if (hipSetDevice(device) != hipSuccess) return -1;
+  const size_t bytes = raw_alloc_bytes(n_words);
+  const size_t after = bytes - (size_t)n_words * 4;  // slack words and guard band
   DevBuf<uint32_t> d;
-  if (d.alloc((n_words * 4 + 15) & ~15ull) != hipSuccess) return -1;
-  launch_fill(d.get(), n_words, base_word, seed, invert ? 1u : 0u);
-  if (hipGetLastError() != hipSuccess) return -1;
-  return hipMemcpy(host_out, d.get(), n_words * 4, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
+  std::vector<unsigned char> back(after);
+  const auto run = [&]() -> hipError_t {
+    TRY(d.alloc(bytes));
+    TRY(hipMemset(d.get(), kGuardByte, bytes));
+    launch_fill(d.get(), n_words, base_word, seed, invert ? 1u : 0u);
+    TRY(hipGetLastError());
+    TRY(hipMemcpy(host_out, d.get(), n_words * 4, hipMemcpyDeviceToHost));
+    return hipMemcpy(back.data(), d.get() + n_words, after, hipMemcpyDeviceToHost);
+  };
+  if (run() != hipSuccess) return -1;
+  int ok = 1;
+  for (size_t i = 0; i < after; ++i) ok &= back[i] == kGuardByte;
+  *guard_ok = ok;
+  return 0;
 }
 
 extern "C" int cro_probe_pattern_verify(int device, unsigned int seed, int invert,
@@ -407,8 +462,9 @@ extern "C" int cro_probe_pattern_verify(int device, unsigned int seed, int inver
   DevBuf<PatternReport> d_rep;
   PatternReport rep = kCleanReport;
   const auto run = [&]() -> hipError_t {
-    TRY(d.alloc((n_words * 4 + 15) & ~15ull));
+    TRY(d.alloc(raw_alloc_bytes(n_words)));
     TRY(d_rep.alloc(sizeof(rep)));
+    TRY(hipMemset(d.get(), kGuardByte, raw_alloc_bytes(n_words)));
     TRY(hipMemcpy(d.get(), host_in, n_words * 4, hipMemcpyHostToDevice));
     TRY(hipMemcpy(d_rep.get(), &rep, sizeof(rep), hipMemcpyHostToDevice));
     launch_verify(d.get(), n_words, base_word, seed, invert ? 1u : 0u, d_rep.get());

@@ -52,8 +52,11 @@ class CroIntegrityOpts(ctypes.Structure):
         ("link_bytes", ctypes.c_longlong),
         ("chunk_bytes", ctypes.c_longlong),
         ("seed", ctypes.c_uint),
-        ("reserved", ctypes.c_int),
+        ("selftest_stage", ctypes.c_int),
         ("link_floor_gbps", ctypes.c_double),
+        ("selftest_pass", ctypes.c_int),
+        ("selftest_bit", ctypes.c_int),
+        ("selftest_word", ctypes.c_ulonglong),
     ]
 
 
@@ -92,6 +95,8 @@ class CroIntegrityResult(ctypes.Structure):
             ("t_total_ms", ctypes.c_double),
             ("failed_stage", ctypes.c_char * 32),
             ("msg", ctypes.c_char * 256),
+            ("first_bad_got", ctypes.c_uint),
+            ("reserved", ctypes.c_int),
         ]
     )
 
@@ -233,7 +238,7 @@ def load_library(required: Optional[bool] = None) -> Optional[ctypes.CDLL]:
     u64p = ctypes.POINTER(ctypes.c_ulonglong)
     lib.cro_probe_pattern_fill.argtypes = [
         ctypes.c_int, ctypes.c_uint, ctypes.c_int,
-        ctypes.c_ulonglong, ctypes.c_ulonglong, u32p,
+        ctypes.c_ulonglong, ctypes.c_ulonglong, u32p, ctypes.POINTER(ctypes.c_int),
     ]
     lib.cro_probe_pattern_fill.restype = ctypes.c_int
     lib.cro_probe_pattern_verify.argtypes = [
@@ -487,18 +492,33 @@ def run_integrity(
     seed: int = 0,
     link_floor_gbps: float = 0.0,
     chunk_bytes: int = 0,
+    selftest_stage=0,
+    selftest_pass: int = 0,
+    selftest_bit: int = 0,
+    selftest_word: int = 0,
 ) -> dict:
     """Deep probe: verify the content of ``vram_bytes`` of VRAM and of
     ``link_bytes`` moved across the host link in both directions, by copy
     engine and by shader (cro_amd/hip/integrity.hip).  Zero sizes take the
-    library defaults.  Gates on data only, unless ``link_floor_gbps`` > 0."""
+    library defaults.  Gates on data only, unless ``link_floor_gbps`` > 0.
+
+    The ``selftest_*`` options are for tests: in ``selftest_stage`` (a name of
+    ``INTEGRITY_STAGES`` or its number, 1-based; 0 is off) the host flips bit
+    ``selftest_bit`` of word ``selftest_word`` of the stage's span between the
+    write and the compare, for VRAM in pass ``selftest_pass``."""
     lib = load_library(required=True)
+    if isinstance(selftest_stage, str):
+        selftest_stage = INTEGRITY_STAGES.index(selftest_stage) + 1
     opts = CroIntegrityOpts(
         vram_bytes=int(vram_bytes),
         link_bytes=int(link_bytes),
         chunk_bytes=int(chunk_bytes),
         seed=int(seed) & 0xFFFFFFFF,
         link_floor_gbps=float(link_floor_gbps),
+        selftest_stage=int(selftest_stage),
+        selftest_pass=int(selftest_pass),
+        selftest_bit=int(selftest_bit),
+        selftest_word=int(selftest_word),
     )
     res = CroIntegrityResult()
     rc = lib.cro_probe_integrity(device, ctypes.byref(opts), ctypes.byref(res))
@@ -522,17 +542,22 @@ def pattern_words(base_word: int, n_words: int, seed: int, invert):
 
 
 def pattern_fill(device: int, seed: int, invert, base_word: int, n_words: int):
-    """Run the fill kernel on ``n_words`` of VRAM and return them (uint32)."""
+    """Run the fill kernel on ``n_words`` of VRAM and return them (uint32).
+    Raises when the kernel wrote anything after word ``n_words`` (the slack of
+    the last vector and a guard band are preset and read back)."""
     import numpy as np
 
     lib = load_library(required=True)
     out = np.zeros(n_words, dtype=np.uint32)
+    guard_ok = ctypes.c_int(0)
     rc = lib.cro_probe_pattern_fill(
         device, seed & 0xFFFFFFFF, 1 if invert else 0, base_word, n_words,
-        out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint)),
+        out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint)), ctypes.byref(guard_ok),
     )
     if rc != 0:
         raise RuntimeError(f"cro_probe_pattern_fill failed: rc={rc}")
+    if not guard_ok.value:
+        raise RuntimeError(f"cro_probe_pattern_fill wrote past its {n_words} words")
     return out
 
 

@@ -757,14 +757,15 @@ def test_build_goes_stale_on_coverage_source_or_header(tmp_path, monkeypatch):
 
     names = {os.path.basename(p) for p in hip_build.ALL_SRCS + hip_build.ALL_HEADERS}
     assert names == {"probe.hip", "integrity.hip", "coverage.hip", "croprobe.h",
-                     "cropattern.h", "crocoverage.h", "crohost.h", "cromfma.h"}
+                     "cropattern.h", "crocoverage.h", "crointegrity.h", "crohost.h",
+                     "cromfma.h"}
     assert all(os.path.exists(p) for p in hip_build.ALL_SRCS + hip_build.ALL_HEADERS)
     # build() and build_agent() look at the new files: stand-ins with chosen
     # mtimes, a hipcc that only records its command line
     lib, agent = tmp_path / "libcroprobe.so", tmp_path / "croagent"
     files = {}
     for name in ("probe.hip", "integrity.hip", "coverage.hip", "croprobe.h", "cropattern.h",
-                 "crocoverage.h", "crohost.h", "cromfma.h", "croagent.cpp"):
+                 "crocoverage.h", "crointegrity.h", "crohost.h", "cromfma.h", "croagent.cpp"):
         files[name] = tmp_path / name
         files[name].write_text("")
         os.utime(files[name], (100, 100))
@@ -780,7 +781,10 @@ def test_build_goes_stale_on_coverage_source_or_header(tmp_path, monkeypatch):
     monkeypatch.setattr(hip_build, "ALL_SRCS", srcs + [str(files["coverage.hip"])])
     internal = [str(files[n]) for n in ("crohost.h", "cromfma.h")]
     monkeypatch.setattr(hip_build, "INTERNAL_HEADERS", internal)
-    monkeypatch.setattr(hip_build, "ALL_HEADERS", hdrs + [str(files["crocoverage.h"])] + internal)
+    monkeypatch.setattr(hip_build, "INTEGRITY_HEADER", str(files["crointegrity.h"]))
+    monkeypatch.setattr(hip_build, "ALL_HEADERS",
+                        hdrs + [str(files["crocoverage.h"]), str(files["crointegrity.h"])]
+                        + internal)
     monkeypatch.setattr(hip_build, "OUT", str(lib))
     monkeypatch.setattr(hip_build, "AGENT_SRC", str(files["croagent.cpp"]))
     monkeypatch.setattr(hip_build, "AGENT_OUT", str(agent))
@@ -795,7 +799,7 @@ def test_build_goes_stale_on_coverage_source_or_header(tmp_path, monkeypatch):
     hip_build.build()
     assert commands == []  # everything up to date
     for newer, want_lib in (("coverage.hip", True), ("crocoverage.h", True),
-                            ("crohost.h", True), ("cromfma.h", True)):
+                            ("crointegrity.h", True), ("crohost.h", True), ("cromfma.h", True)):
         for out in (lib, agent):
             os.utime(out, (200, 200))
         os.utime(files[newer], (300, 300))

@@ -87,6 +87,261 @@ def test_pattern_first_2_20_words_distinct():
     assert np.unique(words).size == 1 << 20
 
 
+# -- host-only header (crointegrity.h) --------------------------------------------
+
+MIB = 1 << 20
+SEED = 0x1234ABCD
+SEED_BACK = SEED ^ 0xA5A5A5A5
+
+INTEGRITY_MAIN = r"""
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+#include "crointegrity.h"
+using namespace crointegrity;
+static unsigned long long num(const char* s) { return strtoull(s, nullptr, 10); }
+int main(int argc, char** argv) {
+  if (argc < 2) return 2;
+  const char* cmd = argv[1];
+  if (!strcmp(cmd, "fill") && argc == 5) {  // n seed invert
+    std::vector<uint32_t> buf(num(argv[2]));
+    host_fill(buf.data(), buf.size(), (uint32_t)num(argv[3]), (uint32_t)num(argv[4]));
+    for (uint32_t w : buf) printf("%u\n", w);
+    return 0;
+  }
+  if (!strcmp(cmd, "verify") && argc == 6) {  // file n seed invert
+    std::vector<uint32_t> buf(num(argv[3]));
+    FILE* f = fopen(argv[2], "rb");
+    if (!f || fread(buf.data(), 4, buf.size(), f) != buf.size()) return 3;
+    fclose(f);
+    const PatternReport r = host_verify(buf.data(), buf.size(), (uint32_t)num(argv[4]),
+                                        (uint32_t)num(argv[5]));
+    printf("%llu %llu %u %u\n", r.n_bad, r.first_bad, r.bits_bad, r.pad);
+    return 0;
+  }
+  if (!strcmp(cmd, "plan") && argc == 4) {  // vram_bytes chunk_bytes (as the options)
+    const Sizes s = normalise_sizes(atoll(argv[2]), 0, atoll(argv[3]));
+    const ChunkPlan plan = chunk_plan(s.vram_words, s.chunk_words);
+    unsigned long long sum = 0, biggest = 0, not_vectors = 0, bad_trips = 0, empty = 0;
+    const unsigned long long count = plan.count();
+    for (unsigned long long c = 0; c < count; ++c) {
+      const unsigned long long n = plan.words(c);
+      if (plan.base(c) != sum) ++bad_trips;  // a chunk starts where the last ended
+      sum += n;
+      if (n > biggest) biggest = n;
+      if (n == 0) ++empty;
+      if (c + 1 < count && n % 4) ++not_vectors;
+      const ChunkPos first = locate(plan, plan.base(c));
+      const ChunkPos last = locate(plan, plan.base(c) + n - 1);
+      if (first.chunk != c || first.word != 0) ++bad_trips;
+      if (last.chunk != c || last.word != n - 1) ++bad_trips;
+    }
+    const ChunkPos end = locate(plan, s.vram_words - 1);
+    if (end.chunk != count - 1 || end.word != plan.words(count - 1) - 1) ++bad_trips;
+    printf("%llu %llu %llu %llu %llu %llu %llu %llu\n", (unsigned long long)s.vram_words,
+           (unsigned long long)s.chunk_words, count, sum, biggest, not_vectors, bad_trips,
+           empty);
+    printf("%llu %llu\n", (unsigned long long)plan.words(0),
+           (unsigned long long)plan.words(count - 1));
+    return 0;
+  }
+  if (!strcmp(cmd, "locate") && argc == 5) {  // vram_bytes chunk_bytes span_word
+    const Sizes s = normalise_sizes(atoll(argv[2]), 0, atoll(argv[3]));
+    const ChunkPos pos = locate(chunk_plan(s.vram_words, s.chunk_words), num(argv[4]));
+    printf("%llu %llu\n", (unsigned long long)pos.chunk, (unsigned long long)pos.word);
+    return 0;
+  }
+  if (!strcmp(cmd, "sizes") && argc == 5) {  // vram_bytes link_bytes chunk_bytes
+    const Sizes s = normalise_sizes(atoll(argv[2]), atoll(argv[3]), atoll(argv[4]));
+    printf("%llu %llu %llu\n", (unsigned long long)s.vram_words,
+           (unsigned long long)s.link_words, (unsigned long long)s.chunk_words);
+    return 0;
+  }
+  if (!strcmp(cmd, "stages") && argc == 3) {  // seed
+    for (int stage = 0; stage < kNumStages; ++stage)
+      for (uint32_t pass = 0; pass < (stage == kVram ? 2u : 1u); ++pass) {
+        const StagePattern p = stage_pattern(stage, pass, (uint32_t)num(argv[2]));
+        printf("%s %u %u %u\n", kStages[stage].name, pass, p.seed, p.invert);
+      }
+    return 0;
+  }
+  return 2;
+}
+"""
+
+
+@pytest.fixture(scope="module")
+def integrity_exe(tmp_path_factory):
+    return _build(tmp_path_factory.mktemp("integrity"), "integrity_main", INTEGRITY_MAIN)
+
+
+def _run(exe, *args):
+    return subprocess.run([exe, *map(str, args)], check=True, capture_output=True,
+                          text=True).stdout
+
+
+@pytest.mark.parametrize("invert", [0, 1])
+@pytest.mark.parametrize("n", [1, 3, 4, 5, 1027])
+def test_host_fill_matches_numpy(integrity_exe, n, invert):
+    got = np.array([int(v) for v in _run(integrity_exe, "fill", n, SEED, invert).split()],
+                   dtype=np.uint32)
+    assert np.array_equal(got, probe_mod.pattern_words(0, n, SEED, invert))
+
+
+def _verify_reference(words, seed, invert):
+    """What a verify of ``words`` as span words 0.. must report, in numpy."""
+    diff = words ^ probe_mod.pattern_words(0, words.size, seed, invert)
+    bad = np.flatnonzero(diff)
+    first = int(bad[0]) if bad.size else (1 << 64) - 1
+    return [int(bad.size), first, int(np.bitwise_or.reduce(diff)), 0]
+
+
+_HV_N = 1027
+# the spread of tests/test_probe_integrity_gpu.py, folded into 1027 words
+_HV_SPREAD = [5, 130, 131, 255, 256, 511, 512, 600, 700, 767, 768, 800, 900, 1000, 1023,
+              1024, 1026]
+
+
+def _host_verify_cases():
+    clean = probe_mod.pattern_words(0, _HV_N, SEED, 0)
+    cases = {"clean": (clean, SEED, 0), "clean inverted":
+             (probe_mod.pattern_words(0, _HV_N, SEED, 1), SEED, 1)}
+    for name, index, bit in (("first", 0, 0), ("middle", 513, 17), ("last", _HV_N - 1, 31)):
+        words = clean.copy()
+        words[index] ^= np.uint32(1 << bit)
+        cases[f"one bit {name}"] = (words, SEED, 0)
+    words = clean.copy()
+    for k, i in enumerate(_HV_SPREAD):
+        words[i] ^= np.uint32((1 << (k % 32)) | (1 << ((3 * k + 7) % 32)))
+    cases["spread"] = (words, SEED, 0)
+    cases["wrong seed"] = (clean, SEED ^ 1, 0)
+    cases["wrong polarity"] = (clean, SEED, 1)
+    return cases
+
+
+HOST_VERIFY_CASES = _host_verify_cases()
+
+
+@pytest.mark.parametrize("name", list(HOST_VERIFY_CASES))
+def test_host_verify_matches_numpy(integrity_exe, tmp_path, name):
+    words, seed, invert = HOST_VERIFY_CASES[name]
+    path = tmp_path / "words.bin"
+    words.tofile(path)
+    got = [int(v) for v in _run(integrity_exe, "verify", path, words.size, seed, invert).split()]
+    want = _verify_reference(words, seed, invert)
+    assert got == want
+    # the reference itself, where the answer is known in closed form
+    if name.startswith("clean"):
+        assert want == [0, (1 << 64) - 1, 0, 0]
+    if name == "one bit last":
+        assert want == [1, _HV_N - 1, 1 << 31, 0]
+    if name == "spread":
+        assert len(set(_HV_SPREAD)) == 17 and want[:2] == [17, 5]
+    if name == "wrong seed":
+        assert want[:2] == [_HV_N, 0]  # the mix is a bijection: every word differs
+    if name == "wrong polarity":
+        assert want == [_HV_N, 0, 0xFFFFFFFF, 0]
+
+
+PLAN_VRAM = [4, 100, 3 * MIB + 20, 3 * MIB + 22, 1 << 30, (1 << 30) + 4, 3 * (1 << 30) + 20]
+PLAN_CHUNK = [0, 5, 16, MIB, MIB + 7, 1 << 30, 1 << 31]
+
+
+def _expected_chunk_words(chunk_bytes):
+    """croprobe.h: 0 or more than 1 GiB is 1 GiB; whole 16-byte vectors, at least one."""
+    if chunk_bytes <= 0 or chunk_bytes > 1 << 30:
+        chunk_bytes = 1 << 30
+    return max(chunk_bytes - chunk_bytes % 16, 16) // 4
+
+
+@pytest.mark.parametrize("chunk_bytes", PLAN_CHUNK)
+@pytest.mark.parametrize("vram_bytes", PLAN_VRAM)
+def test_chunk_plan_and_locate(integrity_exe, vram_bytes, chunk_bytes):
+    lines = _run(integrity_exe, "plan", vram_bytes, chunk_bytes).splitlines()
+    (vram_words, chunk_words, count, total, biggest, not_vectors, bad_trips,
+     empty) = (int(v) for v in lines[0].split())
+    first, last = (int(v) for v in lines[1].split())
+    want_chunk = _expected_chunk_words(chunk_bytes)
+    want_count = -(-(vram_bytes // 4) // want_chunk)
+    assert vram_words == vram_bytes >> 2 and chunk_words == want_chunk
+    assert total == vram_bytes >> 2  # the counts sum to the span, whole words only
+    assert not_vectors == 0  # every chunk but the last is a multiple of 4 words
+    assert biggest <= 1 << 28 and empty == 0
+    assert count == want_count
+    assert bad_trips == 0  # bases are running sums; locate round-trips at every edge
+    assert first == min(want_chunk, vram_words)
+    assert last == vram_words - (want_count - 1) * want_chunk
+    if (vram_bytes, chunk_bytes) == (100, 5):
+        assert (count, first, last) == (7, 4, 1)  # six vectors and one tail word
+    if (vram_bytes, chunk_bytes) in ((3 * MIB + 20, MIB + 7), (3 * MIB + 22, MIB)):
+        assert (count, first, last) == (4, MIB // 4, 5)
+    if (vram_bytes, chunk_bytes) == ((1 << 30) + 4, 0):
+        assert (count, last) == (2, 1)  # a last chunk that is tail only
+
+
+@pytest.mark.parametrize("word,want", [
+    (0, (0, 0)), (MIB // 4 - 1, (0, MIB // 4 - 1)), (MIB // 4, (1, 0)),
+    (2 * (MIB // 4), (2, 0)), (3 * (MIB // 4) - 1, (2, MIB // 4 - 1)),
+    (3 * (MIB // 4), (3, 0)), (3 * (MIB // 4) + 4, (3, 4)),
+])
+def test_locate_known_words(integrity_exe, word, want):
+    got = _run(integrity_exe, "locate", 3 * MIB + 20, MIB, word).split()
+    assert (int(got[0]), int(got[1])) == want
+
+
+def test_sizes_normalised(integrity_exe):
+    def sizes(*args):
+        return tuple(int(v) for v in _run(integrity_exe, "sizes", *args).split())
+
+    assert sizes(0, 0, 0) == ((1 << 30) // 4, (256 * MIB) // 4, (1 << 30) // 4)
+    assert sizes(-5, -5, -5) == sizes(0, 0, 0)
+    assert sizes(7, 4, 15) == (1, 1, 4)
+    assert sizes(3, 3, 16) == (0, 0, 4)  # below one word: the driver refuses
+    assert sizes(3 * MIB + 22, MIB + 23, 31) == ((3 * MIB + 20) // 4, (MIB + 20) // 4, 4)
+
+
+# The documented table (cro_amd/hip/integrity.hip, croprobe.h): VRAM holds the
+# pattern and then its complement; the device→host stages run on
+# seed ^ 0xA5A5A5A5; the shader stages hold the complement.
+STAGE_PATTERNS = {
+    ("vram", 0): (SEED, 0),
+    ("vram", 1): (SEED, 1),
+    ("h2d_dma", 0): (SEED, 0),
+    ("d2h_dma", 0): (SEED_BACK, 0),
+    ("h2d_kernel", 0): (SEED, 1),
+    ("d2h_kernel", 0): (SEED_BACK, 1),
+}
+
+
+def test_stage_seed_and_polarity_table(integrity_exe):
+    got = {}
+    order = []
+    for line in _run(integrity_exe, "stages", SEED).splitlines():
+        name, stage_pass, seed, invert = line.split()
+        got[(name, int(stage_pass))] = (int(seed), int(invert))
+        if name not in order:
+            order.append(name)
+    assert got == STAGE_PATTERNS
+    assert tuple(order) == probe_mod.INTEGRITY_STAGES  # selftest_stage - 1 indexes both
+
+
+def test_guard_preset_differs_from_pattern_at_every_slack_index():
+    """The raw entries preset the 0-3 slack words after n_words to 0xA5 bytes;
+    a verify that read one word too many sees a mismatch only if that is not
+    what the pattern holds there.  It is not, for any shape the GPU tests use."""
+    from tests.test_probe_integrity_gpu import SEED as GPU_SEED, SHAPES
+
+    checked = 0
+    for base, n in SHAPES:
+        slack = -n % 4
+        for invert in (0, 1):
+            words = probe_mod.pattern_words(base + n, slack, GPU_SEED, invert)
+            assert not np.any(words == np.uint32(0xA5A5A5A5)), (base, n, invert)
+            checked += slack
+    assert checked > 0
+
+
 # -- structs --------------------------------------------------------------------
 
 
@@ -109,6 +364,11 @@ def _struct_main():
 def test_struct_layout_matches_ctypes(tmp_path):
     """Every field the ctypes mirrors name exists in the header at the same
     offset and size, and the totals agree (so the header has no extra one)."""
+    opts_fields = [f for f, _ in probe_mod.CroIntegrityOpts._fields_]
+    assert opts_fields[4:] == ["selftest_stage", "link_floor_gbps", "selftest_pass",
+                               "selftest_bit", "selftest_word"]
+    assert [f for f, _ in probe_mod.CroIntegrityResult._fields_][-2:] == ["first_bad_got",
+                                                                         "reserved"]
     exe = _build(tmp_path, "struct_main", _struct_main())
     out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout
     mirrors = {

@@ -463,6 +463,7 @@ INTEGRITY_KEYS = [
     "d2h_dma_n_bad", "h2d_kernel_n_bad", "d2h_kernel_n_bad", "vram_fill_gbps",
     "vram_verify_gbps", "h2d_dma_gbps", "d2h_dma_gbps", "h2d_kernel_gbps", "d2h_kernel_gbps",
     "t_vram_ms", "t_link_dma_ms", "t_link_kernel_ms", "t_total_ms", "failed_stage", "msg",
+    "first_bad_got",
 ]
 COMPUTE_KEYS = [
     "ok", "rc", "cus_expected", "rounds", "waves_run", "waves_bad", "bad_f32", "bad_i8",
