@@ -15,6 +15,9 @@
 //                                            + VRAM / host-link data integrity
 //       [--compute [--compute-min-cu-fraction X]]
 //                                            + exact checks on every CU and SIMD
+//   croagent scrub  [--device N | --bdf B]   overwrite and verify VRAM before drain
+//       [--max-mib N] [--reserve-mib N] [--min-fraction X]
+//                                            (libcroscrub.so, loaded at run time)
 //   croagent drain  --bdf 0000:5a:00.0       sysfs PCI remove
 //   croagent rescan                          sysfs PCI rescan
 //
@@ -22,9 +25,11 @@
 //   hipcc --offload-arch=gfx950 -O2 croagent.cpp -L../hip -lcroprobe -o croagent
 
 #include <dirent.h>
+#include <dlfcn.h>
 #include <unistd.h>
 
 #include "../hip/croprobe.h"
+#include "../hip/croscrub.h"
 
 #include <cinttypes>
 #include <cstdio>
@@ -365,11 +370,68 @@ int cmd_probe_staged(int device, bool compute, const CroComputeOpts& copts, bool
   return ok ? 0 : 1;
 }
 
+// `text` as the inside of a JSON string.
+std::string json_escape(const char* text) {
+  std::string out;
+  for (const char* p = text; *p; ++p) {
+    const unsigned char c = (unsigned char)*p;
+    if (c == '"' || c == '\\') {
+      out += '\\';
+      out += (char)c;
+    } else if (c < 0x20) {
+      out += ' ';
+    } else {
+      out += (char)c;
+    }
+  }
+  return out;
+}
+
+// A scrub that could not start: the same object with only these keys.
+int scrub_unavailable(const std::string& msg) {
+  printf("{\"ok\":false,\"rc\":-1,\"msg\":\"%s\"}\n", json_escape(msg.c_str()).c_str());
+  return 1;
+}
+
+// The result as one JSON object, keys as nodeops/scrub.py run_scrub.
+void print_scrub(const CroScrubResult& r) {
+  printf("{\"ok\":%s,\"rc\":%d,\"vram_total\":%lld,\"vram_free_before\":%lld,"
+         "\"bytes_target\":%lld,\"bytes_scrubbed\":%lld,\"bytes_verified\":%lld,"
+         "\"chunks\":%d,\"alloc_refusals\":%d,\"dirty_words_before\":%llu,",
+         r.ok && r.rc == 0 ? "true" : "false", r.rc, r.vram_total, r.vram_free_before,
+         r.bytes_target, r.bytes_scrubbed, r.bytes_verified, r.chunks, r.alloc_refusals,
+         r.dirty_words_before);
+  printf("\"n_bad\":%llu,\"first_bad_byte\":%llu,\"bits_bad\":%u,\"first_bad_got\":%u,"
+         "\"fraction\":%.6f,\"fill_gbps\":%.1f,\"verify_gbps\":%.1f,\"census_gbps\":%.1f,"
+         "\"t_alloc_ms\":%.1f,\"t_total_ms\":%.1f,\"msg\":\"%s\"}\n",
+         r.n_bad, r.first_bad_byte, r.bits_bad, r.first_bad_got, r.fraction, r.fill_gbps,
+         r.verify_gbps, r.census_gbps, r.t_alloc_ms, r.t_total_ms, json_escape(r.msg).c_str());
+}
+
+// libcroscrub.so is loaded here and not linked, so an agent on a node without
+// it still serves every other subcommand; the agent's RUNPATH finds it next to
+// libcroprobe.so.
+int cmd_scrub(int device, const CroScrubOpts& opts) {
+  void* lib = dlopen("libcroscrub.so", RTLD_NOW | RTLD_LOCAL);
+  if (lib == nullptr) {
+    const char* why = dlerror();
+    return scrub_unavailable(std::string("libcroscrub.so not available: ") + (why ? why : ""));
+  }
+  typedef int (*ScrubRun)(int, const CroScrubOpts*, CroScrubResult*);
+  const ScrubRun run = (ScrubRun)dlsym(lib, "cro_scrub_run");
+  if (run == nullptr)
+    return scrub_unavailable("libcroscrub.so not available: no symbol cro_scrub_run");
+  CroScrubResult result;
+  run(device, &opts, &result);
+  print_scrub(result);
+  return result.ok && result.rc == 0 ? 0 : 1;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
   if (argc < 2) {
-    fprintf(stderr, "usage: croagent <list|cxl|pids|probe|drain|rescan> [options]\n");
+    fprintf(stderr, "usage: croagent <list|cxl|pids|probe|scrub|drain|rescan> [options]\n");
     return 2;
   }
   std::string cmd = argv[1];
@@ -381,6 +443,8 @@ int main(int argc, char** argv) {
   memset(&integ_opts, 0, sizeof(integ_opts));
   CroComputeOpts compute_opts;  // no self-test options here: those are for tests
   memset(&compute_opts, 0, sizeof(compute_opts));
+  CroScrubOpts scrub_opts;  // no self-test options here either
+  memset(&scrub_opts, 0, sizeof(scrub_opts));
   for (int i = 2; i < argc; ++i) {
     std::string arg = argv[i];
     if (arg == "--sysroot" && i + 1 < argc) g_sysroot = argv[++i];
@@ -393,6 +457,9 @@ int main(int argc, char** argv) {
     else if (arg == "--vram-mib" && i + 1 < argc) integ_opts.vram_bytes = atoll(argv[++i]) << 20;
     else if (arg == "--link-mib" && i + 1 < argc) integ_opts.link_bytes = atoll(argv[++i]) << 20;
     else if (arg == "--link-floor-gbps" && i + 1 < argc) integ_opts.link_floor_gbps = atof(argv[++i]);
+    else if (arg == "--max-mib" && i + 1 < argc) scrub_opts.max_bytes = atoll(argv[++i]) << 20;
+    else if (arg == "--reserve-mib" && i + 1 < argc) scrub_opts.reserve_bytes = atoll(argv[++i]) << 20;
+    else if (arg == "--min-fraction" && i + 1 < argc) scrub_opts.min_fraction = atof(argv[++i]);
   }
   if (cmd == "list") return cmd_list();
   if (cmd == "cxl") return cmd_cxl();
@@ -408,6 +475,15 @@ int main(int argc, char** argv) {
       }
     }
     return cmd_probe_staged(device, compute, compute_opts, deep, integ_opts);
+  }
+  if (cmd == "scrub") {
+    if (!bdf.empty()) {
+      std::string lower = bdf;
+      for (auto& c : lower) c = tolower(c);
+      device = resolve_device_by_bdf(lower);
+      if (device < 0) return scrub_unavailable("no HIP device with bdf " + bdf);
+    }
+    return cmd_scrub(device, scrub_opts);
   }
   if (cmd == "drain") return cmd_drain(bdf);
   if (cmd == "rescan") return cmd_rescan();

@@ -92,6 +92,43 @@ def select_probe_fn(args):
     )
 
 
+def add_scrub_arguments(p: argparse.ArgumentParser) -> None:
+    """Scrub on detach: overwrite and verify a GPU's VRAM before it is
+    drained (env defaults are read when the parser is built)."""
+    env = os.environ.get
+    p.add_argument("--scrub-on-detach", choices=["off", "on"],
+                   default=env("CRO_SCRUB_ON_DETACH", "off"),
+                   help="on: before a GPU is drained, fill all the VRAM the "
+                   "driver hands over and read it back; a device that keeps "
+                   "residue is not returned to the fabric pool")
+    p.add_argument("--scrub-max-mib", type=int,
+                   default=int(env("CRO_SCRUB_MAX_MIB", "0")),
+                   help="scrub: at most this many MiB (0 = everything obtainable)")
+    p.add_argument("--scrub-reserve-mib", type=int,
+                   default=int(env("CRO_SCRUB_RESERVE_MIB", "0")),
+                   help="scrub: MiB left unallocated for the runtime "
+                   "(0 or below 256 = 256)")
+    p.add_argument("--scrub-min-fraction", type=float,
+                   default=float(env("CRO_SCRUB_MIN_FRACTION", "0")),
+                   help="scrub: fail when less than this fraction of the "
+                   "device's VRAM was covered (0 = off: coverage is reported, "
+                   "only residue gates)")
+
+
+def select_scrub_fn(args):
+    """The AmdNodeOps scrub hook for the parsed --scrub-* options; None when
+    the scrub is off."""
+    if args.scrub_on_detach != "on":
+        return None
+    from ..nodeops.scrub import make_scrub_fn
+
+    return make_scrub_fn(
+        max_bytes=args.scrub_max_mib << 20,
+        reserve_bytes=args.scrub_reserve_mib << 20,
+        min_fraction=args.scrub_min_fraction,
+    )
+
+
 def main(argv=None) -> int:
     from .. import __version__
 
@@ -146,6 +183,7 @@ def main(argv=None) -> int:
                    "KFD/sysfs (CI and control-plane demos on GPU-less "
                    "machines; BASELINE config #1 shape)")
     add_probe_arguments(p)
+    add_scrub_arguments(p)
     p.add_argument("--max-concurrent-reconciles", type=int, default=8)
     p.add_argument("--syncer-period", type=float, default=60.0)
     p.add_argument("--zap-log-level", default="info")
@@ -317,6 +355,18 @@ def main(argv=None) -> int:
                 log.info("health probe compute-coverage stage: on")
     except Exception:
         log.warning("gfx950 probe library unavailable; health probe disabled")
+    scrub_fn = None
+    if args.scrub_on_detach == "on":
+        try:
+            from ..nodeops.scrub import load_scrub_library
+
+            if load_scrub_library(required=False) is not None:
+                scrub_fn = select_scrub_fn(args)
+                log.info("scrub on detach: on")
+        except Exception:
+            pass
+        if scrub_fn is None:
+            log.warning("gfx950 scrub library unavailable; scrub on detach disabled")
     execer = LocalNodeExec()
     if args.simulate_node_path:
         from ..nodeops.amdgpu import MockNodeOps
@@ -342,6 +392,7 @@ def main(argv=None) -> int:
             cdi_dir=args.cdi_dir,
             destructive=args.destructive,
             probe_fn=probe_fn,
+            scrub_fn=scrub_fn,
         )
         from ..nodeops.composite import CompositeNodeOps
         from ..nodeops.cxl import CxlNodeOps

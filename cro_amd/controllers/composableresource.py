@@ -31,7 +31,7 @@ from ..api.v1alpha1.types import ComposableResource
 from ..fabric import Adapter, FabricError, WaitingDeviceAttaching, WaitingDeviceDetaching
 from ..metrics import Metrics
 from ..nodeops import amdgpu, taints
-from ..nodeops.amdgpu import GPULoadsPresent
+from ..nodeops.amdgpu import GPULoadsPresent, ScrubFailed
 from ..nodeops.nodes import node_exists
 from ..runtime.client import Client
 from ..runtime.controller import Reconciler, Result
@@ -83,6 +83,10 @@ class ComposableResourceReconciler(Reconciler):
         # never corrupts it — the histogram only sees fully observed attaches)
         self._attach_started: Dict[str, float] = {}
         self._detach_started: Dict[str, float] = {}
+        # uids whose device passed its scrub in this detach: the handler is
+        # re-entered on every fabric wait and drain poll, and a device that is
+        # mid-removal must not be scrubbed again
+        self._scrub_done: Dict[str, bool] = {}
         # uid → consecutive fabric-waiting polls (for the exponential wait)
         self._fabric_polls: Dict[str, int] = {}
 
@@ -211,6 +215,56 @@ class ComposableResourceReconciler(Reconciler):
                 )
 
         return span()
+
+    def _scrub_before_drain(self, resource: ComposableResource, ops) -> None:
+        """Overwrite and verify the device's VRAM before it leaves the node,
+        once per detach.  A scrub that does not pass keeps the device here
+        (ScrubFailed) unless the detach is forced."""
+        uid = resource.metadata.uid
+        if self._scrub_done.get(uid):
+            return
+        device_id = resource.status.device_id
+        t0 = time.monotonic()
+        try:
+            result = ops.scrub(resource.spec.target_node, device_id)
+        except Exception as exc:  # a scrub that could not run is a failed scrub
+            result = {"ok": False, "rc": -1, "msg": f"{type(exc).__name__}: {exc}"}
+        if result is None:
+            return  # not configured, or the device is already off the node
+        # the "scrub" phase, recorded only when a scrub ran: with the feature
+        # off the phase histogram keeps exactly the labels it had
+        elapsed = time.monotonic() - t0
+        self.metrics.attach_phase_seconds.labels("scrub").observe(elapsed)
+        self.metrics.scrub_seconds.observe(elapsed)
+        scrubbed = int(result.get("bytes_scrubbed", 0) or 0)
+        self.metrics.scrub_bytes_total.inc(scrubbed)
+        fraction = float(result.get("fraction", 0.0) or 0.0)
+        if result.get("ok"):
+            self._scrub_done[uid] = True
+            self.recorder.normal(
+                resource,
+                "Scrubbed",
+                f"scrubbed {scrubbed / 2**30:.2f} GiB ({100.0 * fraction:.1f} % of VRAM) "
+                f"of device {device_id}, verified; "
+                f"{int(result.get('dirty_words_before', 0) or 0)} dirty words found before; "
+                f"{float(result.get('t_total_ms', 0.0) or 0.0):.0f} ms",
+            )
+            return
+        reason = {-40: "residue", -41: "fraction"}.get(result.get("rc"), "error")
+        self.metrics.scrub_failures_total.labels(reason=reason).inc()
+        # lead with what an operator acts on, before the scrub's own message
+        msg = (
+            f"scrub of device {device_id} failed: {reason} "
+            f"first_bad_byte={result.get('first_bad_byte')} "
+            f"bits_bad=0x{int(result.get('bits_bad', 0) or 0):08x} "
+            f"n_bad={result.get('n_bad')} fraction={fraction:.4f}: {result.get('msg', '')}"
+        )
+        if resource.spec.force_detach:
+            self.recorder.warning(resource, "ScrubFailed", msg + "; force_detach: detaching anyway")
+            self._scrub_done[uid] = True  # force means force, and once
+            return
+        self.recorder.warning(resource, "ScrubFailed", msg)
+        raise ScrubFailed(msg)
 
     def _set_error(self, resource: ComposableResource, msg: str) -> None:
         """requeueOnErr parity: persist the failure into .status.error
@@ -484,6 +538,8 @@ class ComposableResourceReconciler(Reconciler):
             if mode == "DRA":
                 taints.create_device_taint(self.client, resource)
 
+            self._scrub_before_drain(resource, ops)
+
             try:
                 ops.drain(node, resource.status.device_id)
             except amdgpu.DrainInProgress:
@@ -524,6 +580,7 @@ class ComposableResourceReconciler(Reconciler):
             resource.status.cdi_device_id = ""
             resource.status.fabric_wait_started = ""  # wait concluded
             resource = self.client.update_status(resource)
+            self._scrub_done.pop(resource.metadata.uid, None)
             started = self._detach_started.pop(resource.metadata.uid, None)
             if started is not None:
                 self.metrics.detach_seconds.observe(time.monotonic() - started)

@@ -32,6 +32,17 @@ INTEGRITY_HEADER = os.path.join(HIP_DIR, "crointegrity.h")
 ALL_SRCS = SRCS + [COVERAGE_SRC]
 ALL_HEADERS = HEADERS + [COVERAGE_HEADER, INTEGRITY_HEADER] + INTERNAL_HEADERS
 OUT = os.path.join(HIP_DIR, "libcroprobe.so")
+# scrub-on-detach stage: a library of its own (the probe library's lists
+# above are pinned by its tests), with its own staleness check
+SCRUB_SRC = os.path.join(HIP_DIR, "scrub.hip")
+SCRUB_HEADERS = [
+    os.path.join(HIP_DIR, "croscrub.h"),
+    os.path.join(HIP_DIR, "croscrubplan.h"),
+    os.path.join(HIP_DIR, "crohost.h"),
+    INTEGRITY_HEADER,  # for PatternReport
+    HEADERS[1],  # cropattern.h, which crointegrity.h includes
+]
+SCRUB_OUT = os.path.join(HIP_DIR, "libcroscrub.so")
 AGENT_SRC = os.path.join(AGENT_DIR, "croagent.cpp")
 AGENT_OUT = os.path.join(AGENT_DIR, "croagent")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -58,8 +69,22 @@ def build(force: bool = False) -> str:
     return OUT
 
 
+def build_scrub(force: bool = False) -> str:
+    """libcroscrub.so: the scrub-on-detach stage (scrub.hip)."""
+    if force or _stale(SCRUB_OUT, [SCRUB_SRC] + SCRUB_HEADERS):
+        subprocess.run(
+            [HIPCC, *DEVICE_FLAGS, "-fPIC", "-shared", SCRUB_SRC, "-o", SCRUB_OUT],
+            check=True,
+        )
+    return SCRUB_OUT
+
+
 def build_agent(force: bool = False) -> str:
-    """croagent: the native node-agent CLI (links libcroprobe)."""
+    """croagent: the native node-agent CLI (links libcroprobe; loads
+    libcroscrub.so at run time, so that library is no input here, and neither
+    is croscrub.h, which the agent includes: the input list below is pinned by
+    tests/test_probe_compute.py.  A --force build, which is what `make build`
+    does, picks up a change of that header)."""
     if not force and not _stale(AGENT_OUT, [AGENT_SRC, HEADERS[0], COVERAGE_HEADER, OUT]):
         return AGENT_OUT
     subprocess.run(
@@ -84,3 +109,4 @@ if __name__ == "__main__":
     path = build(force="--force" in sys.argv)
     print(path)
     print(AGENT_OUT)
+    print(build_scrub(force="--force" in sys.argv))

@@ -81,6 +81,21 @@ class Metrics:
             "for the optional CU-coverage floor)",
             ["test"],
         )
+        self.scrub_failures_total = Counter(
+            "cro_scrub_failures_total",
+            "Scrubs before drain that did not pass, by reason (residue: words "
+            "still differ after the fill; fraction: less of the VRAM covered "
+            "than the floor asks; error: the scrub could not run)",
+            ["reason"],
+        )
+        self.scrub_seconds = Histogram(
+            "cro_scrub_seconds",
+            "Duration of the scrub before drain, allocation included",
+            buckets=_BUCKETS,
+        )
+        self.scrub_bytes_total = Counter(
+            "cro_scrub_bytes_total", "Bytes of VRAM overwritten by scrubs before drain"
+        )
 
     # test helper: drop collectors so a fresh interpreter state can be faked
     @classmethod
@@ -95,6 +110,9 @@ class Metrics:
                 cls._singleton.devices_online,
                 cls._singleton.probe_integrity_failures_total,
                 cls._singleton.probe_compute_failures_total,
+                cls._singleton.scrub_failures_total,
+                cls._singleton.scrub_seconds,
+                cls._singleton.scrub_bytes_total,
             ):
                 try:
                     REGISTRY.unregister(collector)

@@ -49,6 +49,11 @@ class GPULoadsPresent(Exception):
     pass
 
 
+class ScrubFailed(Exception):
+    """The scrub before drain left residue, covered too little of the VRAM or
+    could not run; the device stays on the node."""
+
+
 class DrainInProgress(Exception):
     """Last-device drain is running asynchronously; re-check shortly."""
 
@@ -91,6 +96,11 @@ class NodeOps:
     def health_probe(self, node: str, device_id: str) -> Optional[dict]:
         return None  # optional capability
 
+    def scrub(self, node: str, device_id: str) -> Optional[dict]:
+        """Overwrite and verify the device's memory before drain; None = not
+        done here (optional capability)."""
+        return None
+
 
 class AmdNodeOps(NodeOps):
     def __init__(
@@ -103,6 +113,7 @@ class AmdNodeOps(NodeOps):
         restart_hooks: Optional[Dict[str, Callable[[str], None]]] = None,
         probe_fn: Optional[Callable[[int], dict]] = None,
         publish_resource_slices: bool = True,
+        scrub_fn: Optional[Callable[[GPUDevice], dict]] = None,
     ):
         self.execer = execer
         self.client = client  # runtime Client for ResourceSlice publication
@@ -115,6 +126,7 @@ class AmdNodeOps(NodeOps):
         # daemonset-restart analogs, keyed by component name
         self.restart_hooks = restart_hooks or {}
         self.probe_fn = probe_fn  # probe_fn(gpu: GPUDevice) -> result dict
+        self.scrub_fn = scrub_fn  # scrub_fn(gpu: GPUDevice) -> result dict
         # gpu_id -> our own host pid holding a KFD context there (or None)
         self._self_pid_cache: Dict[int, Optional[int]] = {}
         # async last-device drains: device_id -> worker thread / error text
@@ -519,6 +531,14 @@ class AmdNodeOps(NodeOps):
         if gpu is None:
             return None
         return self.probe_fn(gpu)
+
+    def scrub(self, node: str, device_id: str) -> Optional[dict]:
+        if self.scrub_fn is None:
+            return None
+        gpu = self.find_gpu(node, device_id)
+        if gpu is None:
+            return None  # already off the node: nothing left to reach
+        return self.scrub_fn(gpu)
 
 
 class MockNodeOps(NodeOps):

@@ -229,3 +229,6 @@ class CxlNodeOps:
 
     def health_probe(self, node: str, device_id: str) -> Optional[dict]:
         return None  # a dax write/read/verify probe is future work
+
+    def scrub(self, node: str, device_id: str) -> Optional[dict]:
+        return None  # the VRAM scrub is the GPU path's
