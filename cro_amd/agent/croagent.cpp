@@ -18,6 +18,8 @@
 //   croagent scrub  [--device N | --bdf B]   overwrite and verify VRAM before drain
 //       [--max-mib N] [--reserve-mib N] [--min-fraction X]
 //                                            (libcroscrub.so, loaded at run time)
+//       [--lds [--lds-min-cu-fraction X]]    + clear and verify every CU's LDS
+//                                            (libcroldsscrub.so, loaded at run time)
 //   croagent drain  --bdf 0000:5a:00.0       sysfs PCI remove
 //   croagent rescan                          sysfs PCI rescan
 //
@@ -29,6 +31,7 @@
 #include <unistd.h>
 
 #include "../hip/croprobe.h"
+#include "../hip/croldsscrub.h"
 #include "../hip/croscrub.h"
 
 #include <cinttypes>
@@ -393,38 +396,85 @@ int scrub_unavailable(const std::string& msg) {
   return 1;
 }
 
-// The result as one JSON object, keys as nodeops/scrub.py run_scrub.
-void print_scrub(const CroScrubResult& r) {
+// The LDS scrub's result as one JSON object, keys as nodeops/ldsscrub.py
+// run_lds_scrub.
+void print_lds_scrub(const CroLdsScrubResult& r) {
+  printf("{\"ok\":%s,\"rc\":%d,\"cus_expected\":%d,\"cus_seen\":%d,\"xcds_seen\":%d,"
+         "\"rounds\":%d,\"lds_bytes\":%d,\"grid\":%d,\"workgroups\":%llu,"
+         "\"bytes_scrubbed\":%llu,\"dirty_words_before\":%llu,\"dirty_workgroups\":%llu,",
+         r.ok && r.rc == 0 ? "true" : "false", r.rc, r.cus_expected, r.cus_seen, r.xcds_seen,
+         r.rounds, r.lds_bytes, r.grid, r.workgroups, r.bytes_scrubbed, r.dirty_words_before,
+         r.dirty_workgroups);
+  printf("\"n_bad\":%llu,\"guard_bad\":%llu,\"recheck_dirty_words\":%llu,"
+         "\"first_dirty_word\":%u,\"first_bad_word\":%u,\"bits_bad\":%u,"
+         "\"bad_workgroups\":%d,\"xcd\":%d,\"se\":%d,\"sh\":%d,\"cu\":%d,"
+         "\"gpu_ms\":%.3f,\"t_total_ms\":%.1f,\"msg\":\"%s\"}",
+         r.n_bad, r.guard_bad, r.recheck_dirty_words, r.first_dirty_word, r.first_bad_word,
+         r.bits_bad, r.bad_workgroups, r.xcd, r.se, r.sh, r.cu, r.gpu_ms, r.t_total_ms,
+         json_escape(r.msg).c_str());
+}
+
+// The result as one JSON object, keys as nodeops/scrub.py run_scrub.  With the
+// LDS scrub's result it is nested under "lds" and merged as nodeops/scrub.py
+// merge_lds_result does: ok only if both passed; rc and msg are the VRAM
+// scrub's when that failed, else the LDS scrub's.  Returns the merged ok.
+bool print_scrub(const CroScrubResult& r, const CroLdsScrubResult* lds) {
+  const bool vram_ok = r.ok && r.rc == 0;
+  const bool ok = vram_ok && (lds == nullptr || (lds->ok && lds->rc == 0));
+  const int rc = vram_ok && lds ? lds->rc : r.rc;
+  const char* msg = vram_ok && lds ? lds->msg : r.msg;
   printf("{\"ok\":%s,\"rc\":%d,\"vram_total\":%lld,\"vram_free_before\":%lld,"
          "\"bytes_target\":%lld,\"bytes_scrubbed\":%lld,\"bytes_verified\":%lld,"
          "\"chunks\":%d,\"alloc_refusals\":%d,\"dirty_words_before\":%llu,",
-         r.ok && r.rc == 0 ? "true" : "false", r.rc, r.vram_total, r.vram_free_before,
+         ok ? "true" : "false", rc, r.vram_total, r.vram_free_before,
          r.bytes_target, r.bytes_scrubbed, r.bytes_verified, r.chunks, r.alloc_refusals,
          r.dirty_words_before);
   printf("\"n_bad\":%llu,\"first_bad_byte\":%llu,\"bits_bad\":%u,\"first_bad_got\":%u,"
          "\"fraction\":%.6f,\"fill_gbps\":%.1f,\"verify_gbps\":%.1f,\"census_gbps\":%.1f,"
-         "\"t_alloc_ms\":%.1f,\"t_total_ms\":%.1f,\"msg\":\"%s\"}\n",
+         "\"t_alloc_ms\":%.1f,\"t_total_ms\":%.1f,\"msg\":\"%s\"",
          r.n_bad, r.first_bad_byte, r.bits_bad, r.first_bad_got, r.fraction, r.fill_gbps,
-         r.verify_gbps, r.census_gbps, r.t_alloc_ms, r.t_total_ms, json_escape(r.msg).c_str());
+         r.verify_gbps, r.census_gbps, r.t_alloc_ms, r.t_total_ms, json_escape(msg).c_str());
+  if (lds) {
+    printf(",\"lds\":");
+    print_lds_scrub(*lds);
+  }
+  printf("}\n");
+  return ok;
 }
 
-// libcroscrub.so is loaded here and not linked, so an agent on a node without
-// it still serves every other subcommand; the agent's RUNPATH finds it next to
-// libcroprobe.so.
-int cmd_scrub(int device, const CroScrubOpts& opts) {
-  void* lib = dlopen("libcroscrub.so", RTLD_NOW | RTLD_LOCAL);
+// `symbol` of `soname`, loaded here and not linked, so an agent on a node
+// without the library still serves every other subcommand; the agent's
+// RUNPATH finds it next to libcroprobe.so.  Null with the reason in *why.
+void* load_entry(const char* soname, const char* symbol, std::string* why) {
+  void* lib = dlopen(soname, RTLD_NOW | RTLD_LOCAL);
   if (lib == nullptr) {
-    const char* why = dlerror();
-    return scrub_unavailable(std::string("libcroscrub.so not available: ") + (why ? why : ""));
+    const char* err = dlerror();
+    *why = std::string(soname) + " not available: " + (err ? err : "");
+    return nullptr;
   }
+  void* entry = dlsym(lib, symbol);
+  if (entry == nullptr) *why = std::string(soname) + " not available: no symbol " + symbol;
+  return entry;
+}
+
+// Both libraries are looked up before anything runs: a scrub that was asked
+// to cover LDS and cannot says so and scrubs nothing.
+int cmd_scrub(int device, const CroScrubOpts& opts, const CroLdsScrubOpts* lds_opts) {
   typedef int (*ScrubRun)(int, const CroScrubOpts*, CroScrubResult*);
-  const ScrubRun run = (ScrubRun)dlsym(lib, "cro_scrub_run");
-  if (run == nullptr)
-    return scrub_unavailable("libcroscrub.so not available: no symbol cro_scrub_run");
+  typedef int (*LdsScrubRun)(int, const CroLdsScrubOpts*, CroLdsScrubResult*);
+  std::string why;
+  const ScrubRun run = (ScrubRun)load_entry("libcroscrub.so", "cro_scrub_run", &why);
+  if (run == nullptr) return scrub_unavailable(why);
+  LdsScrubRun run_lds = nullptr;
+  if (lds_opts) {
+    run_lds = (LdsScrubRun)load_entry("libcroldsscrub.so", "cro_lds_scrub_run", &why);
+    if (run_lds == nullptr) return scrub_unavailable(why);
+  }
   CroScrubResult result;
   run(device, &opts, &result);
-  print_scrub(result);
-  return result.ok && result.rc == 0 ? 0 : 1;
+  CroLdsScrubResult lds_result;
+  if (run_lds) run_lds(device, lds_opts, &lds_result);
+  return print_scrub(result, run_lds ? &lds_result : nullptr) ? 0 : 1;
 }
 
 }  // namespace
@@ -445,6 +495,9 @@ int main(int argc, char** argv) {
   memset(&compute_opts, 0, sizeof(compute_opts));
   CroScrubOpts scrub_opts;  // no self-test options here either
   memset(&scrub_opts, 0, sizeof(scrub_opts));
+  bool lds = false;
+  CroLdsScrubOpts lds_opts;  // nor here
+  memset(&lds_opts, 0, sizeof(lds_opts));
   for (int i = 2; i < argc; ++i) {
     std::string arg = argv[i];
     if (arg == "--sysroot" && i + 1 < argc) g_sysroot = argv[++i];
@@ -460,6 +513,8 @@ int main(int argc, char** argv) {
     else if (arg == "--max-mib" && i + 1 < argc) scrub_opts.max_bytes = atoll(argv[++i]) << 20;
     else if (arg == "--reserve-mib" && i + 1 < argc) scrub_opts.reserve_bytes = atoll(argv[++i]) << 20;
     else if (arg == "--min-fraction" && i + 1 < argc) scrub_opts.min_fraction = atof(argv[++i]);
+    else if (arg == "--lds") lds = true;
+    else if (arg == "--lds-min-cu-fraction" && i + 1 < argc) lds_opts.min_cu_fraction = atof(argv[++i]);
   }
   if (cmd == "list") return cmd_list();
   if (cmd == "cxl") return cmd_cxl();
@@ -483,7 +538,7 @@ int main(int argc, char** argv) {
       device = resolve_device_by_bdf(lower);
       if (device < 0) return scrub_unavailable("no HIP device with bdf " + bdf);
     }
-    return cmd_scrub(device, scrub_opts);
+    return cmd_scrub(device, scrub_opts, lds ? &lds_opts : nullptr);
   }
   if (cmd == "drain") return cmd_drain(bdf);
   if (cmd == "rescan") return cmd_rescan();

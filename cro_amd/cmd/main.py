@@ -113,6 +113,22 @@ def add_scrub_arguments(p: argparse.ArgumentParser) -> None:
                    help="scrub: fail when less than this fraction of the "
                    "device's VRAM was covered (0 = off: coverage is reported, "
                    "only residue gates)")
+    p.add_argument("--scrub-lds", choices=["off", "on"],
+                   default=env("CRO_SCRUB_LDS", "off"),
+                   help="on (needs --scrub-on-detach on): after the VRAM scrub, "
+                   "clear and verify the LDS of every CU; registers are not "
+                   "covered")
+    p.add_argument("--scrub-lds-min-cu-fraction", type=float,
+                   default=float(env("CRO_SCRUB_LDS_MIN_CU_FRACTION", "0")),
+                   help="LDS scrub: fail when less than this fraction of the "
+                   "device's CUs was reached (0 = off: the CUs reached are "
+                   "reported, only residue gates)")
+
+
+def check_scrub_arguments(p: argparse.ArgumentParser, args) -> None:
+    """Start-up errors among the parsed --scrub-* options."""
+    if args.scrub_lds == "on" and args.scrub_on_detach != "on":
+        p.error("--scrub-lds on needs --scrub-on-detach on")
 
 
 def select_scrub_fn(args):
@@ -122,6 +138,14 @@ def select_scrub_fn(args):
         return None
     from ..nodeops.scrub import make_scrub_fn
 
+    if getattr(args, "scrub_lds", "off") == "on":
+        return make_scrub_fn(
+            max_bytes=args.scrub_max_mib << 20,
+            reserve_bytes=args.scrub_reserve_mib << 20,
+            min_fraction=args.scrub_min_fraction,
+            lds=True,
+            lds_min_cu_fraction=args.scrub_lds_min_cu_fraction,
+        )
     return make_scrub_fn(
         max_bytes=args.scrub_max_mib << 20,
         reserve_bytes=args.scrub_reserve_mib << 20,
@@ -195,6 +219,7 @@ def main(argv=None) -> int:
     args = p.parse_args(argv)
     if bool(args.tls_cert_file) != bool(args.tls_key_file):
         p.error("--tls-cert-file and --tls-key-file must be given together")
+    check_scrub_arguments(p, args)
 
     if args.log_format == "json":
         import json as _json
@@ -367,6 +392,20 @@ def main(argv=None) -> int:
             pass
         if scrub_fn is None:
             log.warning("gfx950 scrub library unavailable; scrub on detach disabled")
+        elif args.scrub_lds == "on":
+            lds_lib = None
+            try:
+                from ..nodeops.ldsscrub import load_lds_scrub_library
+
+                lds_lib = load_lds_scrub_library(required=False)
+            except Exception:
+                pass
+            if lds_lib is not None:
+                log.info("scrub on detach: LDS scrub on")
+            else:
+                log.warning("gfx950 LDS scrub library unavailable; LDS scrub disabled")
+                args.scrub_lds = "off"
+                scrub_fn = select_scrub_fn(args)
     execer = LocalNodeExec()
     if args.simulate_node_path:
         from ..nodeops.amdgpu import MockNodeOps

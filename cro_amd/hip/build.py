@@ -43,6 +43,15 @@ SCRUB_HEADERS = [
     HEADERS[1],  # cropattern.h, which crointegrity.h includes
 ]
 SCRUB_OUT = os.path.join(HIP_DIR, "libcroscrub.so")
+# LDS scrub stage: again a library of its own (the scrub library's list above
+# is pinned by its tests too)
+LDS_SCRUB_SRC = os.path.join(HIP_DIR, "ldsscrub.hip")
+LDS_SCRUB_HEADERS = [
+    os.path.join(HIP_DIR, "croldsscrub.h"),
+    os.path.join(HIP_DIR, "crohost.h"),
+    COVERAGE_HEADER,  # for cro_cov_cu_key and cro_cov_decode
+]
+LDS_SCRUB_OUT = os.path.join(HIP_DIR, "libcroldsscrub.so")
 AGENT_SRC = os.path.join(AGENT_DIR, "croagent.cpp")
 AGENT_OUT = os.path.join(AGENT_DIR, "croagent")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -79,12 +88,23 @@ def build_scrub(force: bool = False) -> str:
     return SCRUB_OUT
 
 
+def build_lds_scrub(force: bool = False) -> str:
+    """libcroldsscrub.so: the LDS scrub stage (ldsscrub.hip)."""
+    if force or _stale(LDS_SCRUB_OUT, [LDS_SCRUB_SRC] + LDS_SCRUB_HEADERS):
+        subprocess.run(
+            [HIPCC, *DEVICE_FLAGS, "-fPIC", "-shared", LDS_SCRUB_SRC, "-o", LDS_SCRUB_OUT],
+            check=True,
+        )
+    return LDS_SCRUB_OUT
+
+
 def build_agent(force: bool = False) -> str:
     """croagent: the native node-agent CLI (links libcroprobe; loads
-    libcroscrub.so at run time, so that library is no input here, and neither
-    is croscrub.h, which the agent includes: the input list below is pinned by
+    libcroscrub.so and libcroldsscrub.so at run time, so those libraries are
+    no inputs here, and neither are croscrub.h and croldsscrub.h, which the
+    agent includes: the input list below is pinned by
     tests/test_probe_compute.py.  A --force build, which is what `make build`
-    does, picks up a change of that header)."""
+    does, picks up a change of those headers)."""
     if not force and not _stale(AGENT_OUT, [AGENT_SRC, HEADERS[0], COVERAGE_HEADER, OUT]):
         return AGENT_OUT
     subprocess.run(
@@ -110,3 +130,4 @@ if __name__ == "__main__":
     print(path)
     print(AGENT_OUT)
     print(build_scrub(force="--force" in sys.argv))
+    print(build_lds_scrub(force="--force" in sys.argv))

@@ -85,7 +85,9 @@ class Metrics:
             "cro_scrub_failures_total",
             "Scrubs before drain that did not pass, by reason (residue: words "
             "still differ after the fill; fraction: less of the VRAM covered "
-            "than the floor asks; error: the scrub could not run)",
+            "than the floor asks; lds_residue: LDS words still differ after "
+            "the fill or at the recheck; lds_coverage: fewer CUs reached than "
+            "the floor asks; error: the scrub could not run)",
             ["reason"],
         )
         self.scrub_seconds = Histogram(

@@ -196,24 +196,47 @@ def scrub_report(words, fill_word: int, base_word: int = 0) -> dict:
 # -- node-ops hooks ---------------------------------------------------------------
 
 
-def make_scrub_fn(max_bytes: int = 0, reserve_bytes: int = 0, min_fraction: float = 0.0):
-    """AmdNodeOps scrub hook: GPUDevice → scrub result on the right ordinal."""
+def merge_lds_result(vram: dict, lds: dict) -> dict:
+    """The VRAM scrub's result with the LDS scrub's nested under ``"lds"``:
+    ``ok`` only if both passed; ``rc`` and ``msg`` are the VRAM scrub's when
+    that failed, else the LDS scrub's."""
+    out = dict(vram)
+    out["lds"] = lds
+    out["ok"] = bool(vram.get("ok")) and bool(lds.get("ok"))
+    if vram.get("ok"):
+        out["rc"] = lds.get("rc")
+        out["msg"] = lds.get("msg", "")
+    return out
+
+
+def make_scrub_fn(max_bytes: int = 0, reserve_bytes: int = 0, min_fraction: float = 0.0,
+                  lds: bool = False, lds_min_cu_fraction: float = 0.0):
+    """AmdNodeOps scrub hook: GPUDevice → scrub result on the right ordinal.
+    ``lds``: the LDS scrub (nodeops/ldsscrub.py) runs after the VRAM scrub and
+    its result is merged in (merge_lds_result)."""
 
     def scrub(gpu) -> dict:
         dev = hip_device_for_bdf(gpu.pci_bdf)
         if dev is None:
             dev = 0
-        return run_scrub(dev, max_bytes=max_bytes, reserve_bytes=reserve_bytes,
-                         min_fraction=min_fraction)
+        result = run_scrub(dev, max_bytes=max_bytes, reserve_bytes=reserve_bytes,
+                           min_fraction=min_fraction)
+        if not lds:
+            return result
+        from . import ldsscrub
+
+        return merge_lds_result(
+            result, ldsscrub.run_lds_scrub(dev, min_cu_fraction=lds_min_cu_fraction))
 
     return scrub
 
 
 def scrub_via_exec(execer, node: str, gpu, argv_prefix=None, max_mib=None, reserve_mib=None,
-                   min_fraction=0) -> dict:
+                   min_fraction=0, lds=False, lds_min_cu_fraction=0.0) -> dict:
     """Scrub through the node agent (``croagent scrub --bdf``), for
-    controllers that run off-node.  Returns the same dict shape as run_scrub;
-    ``argv_prefix`` as in probe.probe_via_exec."""
+    controllers that run off-node.  Returns the same dict shape as run_scrub
+    (with ``lds``: as make_scrub_fn's, merged by the agent); ``argv_prefix`` as
+    in probe.probe_via_exec."""
     import json as _json
 
     argv = list(argv_prefix or []) + ["croagent", "scrub", "--bdf", gpu.pci_bdf]
@@ -223,6 +246,10 @@ def scrub_via_exec(execer, node: str, gpu, argv_prefix=None, max_mib=None, reser
         argv += ["--reserve-mib", str(int(reserve_mib))]
     if min_fraction:
         argv += ["--min-fraction", str(float(min_fraction))]
+    if lds:
+        argv += ["--lds"]
+        if lds_min_cu_fraction:
+            argv += ["--lds-min-cu-fraction", str(float(lds_min_cu_fraction))]
     rc, out, err = execer.run(node, argv, timeout=300)
     if not out.strip():
         return {"ok": False, "rc": rc, "msg": err.strip() or "croagent scrub failed"}
@@ -236,13 +263,17 @@ def scrub_via_exec(execer, node: str, gpu, argv_prefix=None, max_mib=None, reser
 
 
 def make_exec_scrub_fn(execer, node: str, argv_prefix_fn=None, max_mib=None, reserve_mib=None,
-                       min_fraction=0):
+                       min_fraction=0, lds=False, lds_min_cu_fraction=0.0):
     """AmdNodeOps scrub hook bound to a NodeExec (local or remote agent);
     ``argv_prefix_fn`` as in probe.make_exec_probe_fn."""
 
     def scrub(gpu):
         prefix = argv_prefix_fn() if argv_prefix_fn else None
+        if not lds:
+            return scrub_via_exec(execer, node, gpu, argv_prefix=prefix, max_mib=max_mib,
+                                  reserve_mib=reserve_mib, min_fraction=min_fraction)
         return scrub_via_exec(execer, node, gpu, argv_prefix=prefix, max_mib=max_mib,
-                              reserve_mib=reserve_mib, min_fraction=min_fraction)
+                              reserve_mib=reserve_mib, min_fraction=min_fraction, lds=True,
+                              lds_min_cu_fraction=lds_min_cu_fraction)
 
     return scrub
