@@ -26,6 +26,12 @@
 // The location is for the report only; HIP promises nothing about placement,
 // so coverage gates only when the caller sets min_cu_fraction.
 //
+// For tests the kernel is a template: its second instantiation can make LDS
+// words wrong between fill and verify (self-test modes 3 and 4) or copy LDS
+// out after a fill (cro_probe_compute_lds_dump), and the host can hand the
+// kernel the caller's expected tiles (cro_probe_compute_tiles); croprobe.h.
+// A run without a plant launches the first instantiation.
+//
 // Compiled with probe.hip and integrity.hip into libcroprobe.so; host plumbing
 // shared with them in crohost.h, one wave's matrix products and result maps
 // shared with probe.hip in cromfma.h.
@@ -49,6 +55,10 @@ constexpr int kDefaultRounds = 4;
 constexpr int kMaxRounds = 64;
 constexpr int kMaxGrid = 1 << 16;
 constexpr int kMaxIters = 1 << 16;
+// the dump entry's guard: 256 words after the marched ones (as croldsscrub.h)
+constexpr uint32_t kGuardWord = 0xA5A5A5A5u;
+constexpr int kGuardBytes = 1024;
+constexpr int kMaxDumpGrid = 8;
 
 // one wave of the coverage kernel's i8 or bf16 product (cromfma.h), stored
 // through the result maps: the raw tile entry's kernel
@@ -87,6 +97,13 @@ struct CovParams {
   uint32_t inj_elem;
   uint32_t inj_flip;  // 1 << selftest_bit
   uint32_t inj_key;
+  // test seams, read by coverage_kernel<true> only
+  uint32_t inj_span;   // modes 3 and 4: words planted from inj_elem on
+  uint32_t inj_pass;   // 0 pattern, 1 complement, 2 both
+  uint32_t* dump_out;  // not null: copy LDS out after the fill of dump_pass, and return
+  uint32_t dump_pass;
+  uint32_t guard_vecs;  // vectors after the marched ones, preset and counted
+  unsigned int* guard_bad;
 };
 
 // What one wave found in one test.  n_bad is wave-uniform (ballot counts);
@@ -126,6 +143,11 @@ __device__ inline uint4 lds_want(uint64_t base_word, uint32_t v, uint32_t seed,
   return cro_pattern_vec4(base_word + ((uint64_t)v << 2), seed, invert);
 }
 
+// kSeams = false is the stage's kernel.  kSeams = true adds, between the
+// fill's barrier and the verify loop, what the tests of the march need: the
+// LDS plant of self-test modes 3 and 4 and the dump (croprobe.h).  The fill
+// and verify loops are the same source in both.
+template <bool kSeams>
 __global__ __launch_bounds__(kBlock) void coverage_kernel(CovParams p) {
   // all LDS is dynamic, so its base stays 16-byte aligned for the b128 accesses
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -161,6 +183,15 @@ __global__ __launch_bounds__(kBlock) void coverage_kernel(CovParams p) {
   Tally t_f32, t_i8, t_bf16, t_lds;
   const uint32_t n4 = p.lds_words >> 2;
   const uint64_t lds_base = (uint64_t)blockIdx.x * p.lds_words;
+
+  // A workgroup runs on one CU, so this is the same in all of its threads:
+  // the plant's barrier below is reached by every one of them or by none.
+  bool plant = false;
+  if constexpr (kSeams) {
+    plant = p.inj_mode == 3 || (p.inj_mode == 4 && cro_cov_cu_key(xcc_id, hw_id) == p.inj_key);
+    for (uint32_t v = n4 + tid; v < n4 + p.guard_vecs; v += kBlock)
+      lds4[v] = make_uint4(kGuardWord, kGuardWord, kGuardWord, kGuardWord);
+  }
 
   for (uint32_t it = 0; it < p.iters; ++it) {
     // an offset of zero the compiler cannot see through: the products are
@@ -205,6 +236,31 @@ __global__ __launch_bounds__(kBlock) void coverage_kernel(CovParams p) {
     for (uint32_t invert = 0; invert < 2; ++invert) {
       for (uint32_t v = tid; v < n4; v += kBlock) lds4[v] = lds_want(lds_base, v, p.seed, invert);
       __syncthreads();
+      if constexpr (kSeams) {
+        if (plant && (p.inj_pass == 2 || p.inj_pass == invert)) {
+          // vector v is altered by thread (v + 128) % 256, two waves away from
+          // the wave that verifies it; only the planted words are stored
+          uint32_t* lds1 = reinterpret_cast<uint32_t*>(smem);
+          const uint32_t lo = p.inj_elem, hi = p.inj_elem + p.inj_span;  // hi <= lds_words
+          for (uint32_t v = ((lo >> 2) & ~(uint32_t)(kBlock - 1)) | (tid ^ 128u);
+               (v << 2) < hi; v += kBlock)
+            for (uint32_t w = v << 2; w < (v << 2) + 4; ++w)
+              if (w >= lo && w < hi) lds1[w] ^= p.inj_flip;
+          __syncthreads();
+        }
+        if (p.dump_out != nullptr && p.dump_pass == invert) {
+          uint4* dst = reinterpret_cast<uint4*>(p.dump_out) + (size_t)blockIdx.x * n4;
+          for (uint32_t v = tid; v < n4; v += kBlock) dst[v] = lds4[v];
+          uint32_t changed = 0;
+          for (uint32_t v = n4 + tid; v < n4 + p.guard_vecs; v += kBlock) {
+            const uint4 g = lds4[v];
+            changed += (g.x != kGuardWord) + (g.y != kGuardWord) + (g.z != kGuardWord) +
+                       (g.w != kGuardWord);
+          }
+          if (changed) atomicAdd(p.guard_bad, changed);
+          return;
+        }
+      }
       for (uint32_t v0 = tid - lane; v0 < n4; v0 += kBlock) {
         const uint32_t v = v0 + lane;
         const uint4 want = lds_want(lds_base, v, p.seed, invert);
@@ -258,7 +314,11 @@ struct CovCtx : CtxBase {
   int* dE8 = nullptr;
   uint16_t *dA16 = nullptr, *dB16 = nullptr;
   float* dE16 = nullptr;
-  void* dEx = nullptr;  // self-test mode 1: the altered copy of one expected tile
+  // one call's own expected tiles (the caller's, or self-test mode 1's copy
+  // with one bit flipped); the cached tiles above stay
+  float* dX32 = nullptr;
+  int* dX8 = nullptr;
+  float* dX16 = nullptr;
   float hE32[CRO_COV_F32_ELEMS];
   int hE8[CRO_COV_I8_ELEMS];
   float hE16[CRO_COV_BF16_ELEMS];
@@ -294,8 +354,74 @@ int upload_tiles(CovCtx* ctx, uint32_t seed, CroComputeResult* out) {
   return 0;
 }
 
-int run_compute(int device, const CroComputeOpts* opts, CroComputeResult* out,
-                CroCoverageRecord* records_out, int max_records) {
+// The caller's expected tiles of cro_probe_compute_tiles; null = the cached one.
+struct CallerTiles {
+  const float* e32 = nullptr;
+  const int* e8 = nullptr;
+  const float* e16 = nullptr;
+};
+
+// First use of a device, and the tiles of `seed`; the slot's lock is held.
+int prepare(CovCtx* ctx, int device, uint32_t seed, CroComputeResult* out) {
+  if (!ctx->ready) {
+    hipDeviceProp_t prop;
+    CHECK(hipGetDeviceProperties(&prop, device));
+    ctx->cus = prop.multiProcessorCount;
+    CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(coverage_kernel<false>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize,
+                               CRO_COV_MAX_LDS_BYTES));
+    CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(coverage_kernel<true>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize,
+                               CRO_COV_MAX_LDS_BYTES));
+    CHECK(hipEventCreate(&ctx->e0));
+    CHECK(hipEventCreate(&ctx->e1));
+    CHECK(hipMalloc(&ctx->dA32, 16 * CRO_COV_F32_K * sizeof(float)));
+    CHECK(hipMalloc(&ctx->dB32, CRO_COV_F32_K * 16 * sizeof(float)));
+    CHECK(hipMalloc(&ctx->dE32, sizeof(ctx->hE32)));
+    CHECK(hipMalloc(&ctx->dA8, 16 * CRO_COV_I8_K));
+    CHECK(hipMalloc(&ctx->dB8, CRO_COV_I8_K * 16));
+    CHECK(hipMalloc(&ctx->dE8, sizeof(ctx->hE8)));
+    CHECK(hipMalloc(&ctx->dA16, 32 * CRO_COV_BF16_K * sizeof(uint16_t)));
+    CHECK(hipMalloc(&ctx->dB16, CRO_COV_BF16_K * 32 * sizeof(uint16_t)));
+    CHECK(hipMalloc(&ctx->dE16, sizeof(ctx->hE16)));
+    CHECK(hipMalloc(&ctx->dX32, sizeof(ctx->hE32)));
+    CHECK(hipMalloc(&ctx->dX8, sizeof(ctx->hE8)));
+    CHECK(hipMalloc(&ctx->dX16, sizeof(ctx->hE16)));
+    ctx->ready = 1;
+  }
+  if (!ctx->tiles_ready || ctx->seed != seed) {
+    ctx->tiles_ready = 0;
+    if (upload_tiles(ctx, seed, out) != 0) return -1;
+  }
+  return 0;
+}
+
+// The record buffer holds at least n records afterwards.
+int reserve_records(CovCtx* ctx, size_t n, CroComputeResult* out) {
+  if (ctx->records_cap >= n) return 0;
+  if (ctx->d_records) (void)hipFree(ctx->d_records);
+  ctx->d_records = nullptr;
+  ctx->records_cap = 0;
+  CHECK(hipMalloc(&ctx->d_records, n * sizeof(CroCoverageRecord)));
+  ctx->records_cap = n;
+  return 0;
+}
+
+void set_inputs(const CovCtx* ctx, CovParams* p) {
+  memset(p, 0, sizeof(*p));
+  p->A32 = ctx->dA32;
+  p->B32 = ctx->dB32;
+  p->E32 = ctx->dE32;
+  p->A8 = ctx->dA8;
+  p->B8 = ctx->dB8;
+  p->E8 = ctx->dE8;
+  p->A16 = ctx->dA16;
+  p->B16 = ctx->dB16;
+  p->E16 = ctx->dE16;
+}
+
+int run_compute(int device, const CroComputeOpts* opts, const CallerTiles& tiles,
+                CroComputeResult* out, CroCoverageRecord* records_out, int max_records) {
   CroComputeOpts o;
   memset(&o, 0, sizeof(o));
   if (opts) o = *opts;
@@ -310,7 +436,8 @@ int run_compute(int device, const CroComputeOpts* opts, CroComputeResult* out,
   const int max_rounds = o.max_rounds ? o.max_rounds : kDefaultRounds;
   // the self-test only ever names an element that exists: the host indexes
   // the expected tile with it
-  if (o.selftest_mode < 0 || o.selftest_mode > 2) return bad_arg(out, "selftest_mode");
+  if (o.selftest_mode < 0 || o.selftest_mode > 4) return bad_arg(out, "selftest_mode");
+  const bool plant = o.selftest_mode >= 3;  // real LDS stores: the LDS test only
   if (o.selftest_mode) {
     const uint32_t elems[CRO_COV_TESTS] = {CRO_COV_F32_ELEMS, CRO_COV_I8_ELEMS,
                                            CRO_COV_BF16_ELEMS, (uint32_t)lds_bytes / 4};
@@ -318,62 +445,31 @@ int run_compute(int device, const CroComputeOpts* opts, CroComputeResult* out,
       return bad_arg(out, "selftest_test");
     if (o.selftest_bit < 0 || o.selftest_bit > 31) return bad_arg(out, "selftest_bit");
     if (o.selftest_elem >= elems[o.selftest_test]) return bad_arg(out, "selftest_elem");
+    if (plant) {
+      if (o.selftest_test != CRO_COV_TEST_LDS)
+        return bad_arg(out, "selftest_test: modes 3 and 4 plant in LDS");
+      if (o.selftest_span < 1 || o.selftest_span > elems[CRO_COV_TEST_LDS] - o.selftest_elem)
+        return bad_arg(out, "selftest_span");
+      if (o.selftest_pass < 0 || o.selftest_pass > 2) return bad_arg(out, "selftest_pass");
+    }
   }
 
   std::unique_lock<std::mutex> lock;
   CovCtx* ctx = enter_device(g_cctx, device, lock, out->msg, sizeof(out->msg));
   if (ctx == nullptr) return -1;
-  if (!ctx->ready) {
-    hipDeviceProp_t prop;
-    CHECK(hipGetDeviceProperties(&prop, device));
-    ctx->cus = prop.multiProcessorCount;
-    CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(coverage_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize,
-                               CRO_COV_MAX_LDS_BYTES));
-    CHECK(hipEventCreate(&ctx->e0));
-    CHECK(hipEventCreate(&ctx->e1));
-    CHECK(hipMalloc(&ctx->dA32, 16 * CRO_COV_F32_K * sizeof(float)));
-    CHECK(hipMalloc(&ctx->dB32, CRO_COV_F32_K * 16 * sizeof(float)));
-    CHECK(hipMalloc(&ctx->dE32, sizeof(ctx->hE32)));
-    CHECK(hipMalloc(&ctx->dA8, 16 * CRO_COV_I8_K));
-    CHECK(hipMalloc(&ctx->dB8, CRO_COV_I8_K * 16));
-    CHECK(hipMalloc(&ctx->dE8, sizeof(ctx->hE8)));
-    CHECK(hipMalloc(&ctx->dA16, 32 * CRO_COV_BF16_K * sizeof(uint16_t)));
-    CHECK(hipMalloc(&ctx->dB16, CRO_COV_BF16_K * 32 * sizeof(uint16_t)));
-    CHECK(hipMalloc(&ctx->dE16, sizeof(ctx->hE16)));
-    CHECK(hipMalloc(&ctx->dEx, sizeof(ctx->hE16)));  // the largest tile
-    ctx->ready = 1;
-  }
-  if (!ctx->tiles_ready || ctx->seed != o.seed) {
-    ctx->tiles_ready = 0;
-    if (upload_tiles(ctx, o.seed, out) != 0) return -1;
-  }
+  if (prepare(ctx, device, o.seed, out) != 0) return -1;
   const int grid = o.grid_blocks ? o.grid_blocks : ctx->cus;
   if (grid < 1) return bad_arg(out, "device reports no compute units");
   const size_t per_round = (size_t)grid * kWaves;
   const size_t n_max = per_round * (size_t)max_rounds;
-  if (ctx->records_cap < n_max) {
-    if (ctx->d_records) (void)hipFree(ctx->d_records);
-    ctx->d_records = nullptr;
-    ctx->records_cap = 0;
-    CHECK(hipMalloc(&ctx->d_records, n_max * sizeof(CroCoverageRecord)));
-    ctx->records_cap = n_max;
-  }
+  if (reserve_records(ctx, n_max, out) != 0) return -1;
   out->cus_expected = ctx->cus;
   out->grid_blocks = grid;
   out->lds_bytes = lds_bytes;
   out->iters = iters;
 
   CovParams p;
-  p.A32 = ctx->dA32;
-  p.B32 = ctx->dB32;
-  p.E32 = ctx->dE32;
-  p.A8 = ctx->dA8;
-  p.B8 = ctx->dB8;
-  p.E8 = ctx->dE8;
-  p.A16 = ctx->dA16;
-  p.B16 = ctx->dB16;
-  p.E16 = ctx->dE16;
+  set_inputs(ctx, &p);
   p.lds_words = (uint32_t)lds_bytes / 4;
   p.iters = (uint32_t)iters;
   p.seed = o.seed;
@@ -382,25 +478,29 @@ int run_compute(int device, const CroComputeOpts* opts, CroComputeResult* out,
   p.inj_elem = o.selftest_elem;
   p.inj_flip = 1u << (o.selftest_bit & 31);
   p.inj_key = o.selftest_key;
-  if (o.selftest_mode == 1 && o.selftest_test != CRO_COV_TEST_LDS) {
-    // flip one bit of one expected element in a copy; the cached tile stays
+  p.inj_span = o.selftest_span;
+  p.inj_pass = (uint32_t)o.selftest_pass;
+  // This call's own expected tiles: the caller's, or for self-test mode 1 a
+  // copy with one bit of one element flipped.  The kernel sees a pointer.
+  const bool flip = o.selftest_mode == 1 && o.selftest_test != CRO_COV_TEST_LDS;
+  const auto own_tile = [&](int test, const void* caller, const void* cached, void* dev,
+                            size_t bytes) -> hipError_t {
     uint32_t alt[CRO_COV_BF16_ELEMS];
-    size_t bytes = 0;
-    if (o.selftest_test == CRO_COV_TEST_F32) {
-      bytes = sizeof(ctx->hE32);
-      memcpy(alt, ctx->hE32, bytes);
-      p.E32 = (const float*)ctx->dEx;
-    } else if (o.selftest_test == CRO_COV_TEST_I8) {
-      bytes = sizeof(ctx->hE8);
-      memcpy(alt, ctx->hE8, bytes);
-      p.E8 = (const int*)ctx->dEx;
-    } else {
-      bytes = sizeof(ctx->hE16);
-      memcpy(alt, ctx->hE16, bytes);
-      p.E16 = (const float*)ctx->dEx;
-    }
-    alt[o.selftest_elem] ^= p.inj_flip;
-    CHECK(hipMemcpy(ctx->dEx, alt, bytes, hipMemcpyHostToDevice));
+    memcpy(alt, caller ? caller : cached, bytes);
+    if (flip && o.selftest_test == test) alt[o.selftest_elem] ^= p.inj_flip;
+    return hipMemcpy(dev, alt, bytes, hipMemcpyHostToDevice);
+  };
+  if (tiles.e32 || (flip && o.selftest_test == CRO_COV_TEST_F32)) {
+    CHECK(own_tile(CRO_COV_TEST_F32, tiles.e32, ctx->hE32, ctx->dX32, sizeof(ctx->hE32)));
+    p.E32 = ctx->dX32;
+  }
+  if (tiles.e8 || (flip && o.selftest_test == CRO_COV_TEST_I8)) {
+    CHECK(own_tile(CRO_COV_TEST_I8, tiles.e8, ctx->hE8, ctx->dX8, sizeof(ctx->hE8)));
+    p.E8 = ctx->dX8;
+  }
+  if (tiles.e16 || (flip && o.selftest_test == CRO_COV_TEST_BF16)) {
+    CHECK(own_tile(CRO_COV_TEST_BF16, tiles.e16, ctx->hE16, ctx->dX16, sizeof(ctx->hE16)));
+    p.E16 = ctx->dX16;
   }
 
   std::vector<CroCoverageRecord> records(n_max);
@@ -410,7 +510,12 @@ int run_compute(int device, const CroComputeOpts* opts, CroComputeResult* out,
   for (;;) {
     p.records = ctx->d_records + (size_t)rounds * per_round;
     const auto one_round = [&] {
-      hipLaunchKernelGGL(coverage_kernel, dim3(grid), dim3(kBlock), (size_t)lds_bytes, 0, p);
+      if (plant)
+        hipLaunchKernelGGL(coverage_kernel<true>, dim3(grid), dim3(kBlock), (size_t)lds_bytes, 0,
+                           p);
+      else
+        hipLaunchKernelGGL(coverage_kernel<false>, dim3(grid), dim3(kBlock), (size_t)lds_bytes,
+                           0, p);
     };
     float ms = 0.f;
     CHECK(timed_ms(*ctx, &ms, one_round));
@@ -459,21 +564,100 @@ int run_compute(int device, const CroComputeOpts* opts, CroComputeResult* out,
   return 0;
 }
 
-}  // namespace
+int run_lds_dump(int device, int grid_blocks, int lds_bytes, uint32_t seed, int pass,
+                 uint32_t plant_elem, uint32_t plant_span, int plant_bit, uint32_t* host_out,
+                 unsigned int* guard_bad_out, CroComputeResult* out) {
+  if (grid_blocks < 1 || grid_blocks > kMaxDumpGrid) return -10;
+  if (lds_bytes < 16 || lds_bytes > CRO_COV_MAX_LDS_BYTES || (lds_bytes & 15)) return -10;
+  if (pass < 0 || pass > 1 || host_out == nullptr || guard_bad_out == nullptr) return -10;
+  const uint32_t lds_words = (uint32_t)lds_bytes / 4;
+  if (plant_span) {
+    if (plant_bit < 0 || plant_bit > 31) return -10;
+    if (plant_elem >= lds_words || plant_span > lds_words - plant_elem) return -10;
+  }
+  const bool guarded = lds_bytes <= CRO_COV_MAX_LDS_BYTES - kGuardBytes;
 
-extern "C" int cro_probe_compute_records(int device, const struct CroComputeOpts* opts,
-                                         struct CroComputeResult* out,
-                                         struct CroCoverageRecord* records_out,
-                                         int max_records) {
+  std::unique_lock<std::mutex> lock;
+  CovCtx* ctx = enter_device(g_cctx, device, lock, out->msg, sizeof(out->msg));
+  if (ctx == nullptr) return -1;
+  if (prepare(ctx, device, seed, out) != 0) return -1;
+  if (reserve_records(ctx, (size_t)grid_blocks * kWaves, out) != 0) return -1;
+  const size_t dump_bytes = (size_t)grid_blocks * lds_bytes;
+  DevBuf<uint32_t> d_dump;
+  DevBuf<unsigned int> d_guard;
+  CHECK(d_dump.alloc(dump_bytes));
+  CHECK(d_guard.alloc(sizeof(unsigned int)));
+  CHECK(hipMemset(d_dump.get(), 0, dump_bytes));
+  CHECK(hipMemset(d_guard.get(), 0, sizeof(unsigned int)));
+
+  CovParams p;
+  set_inputs(ctx, &p);
+  p.records = ctx->d_records;  // the kernel returns before it writes one
+  p.lds_words = lds_words;
+  p.iters = 1;
+  p.seed = seed;
+  p.inj_mode = plant_span ? 3u : 0u;
+  p.inj_test = CRO_COV_TEST_LDS;
+  p.inj_elem = plant_elem;
+  p.inj_flip = 1u << (plant_bit & 31);
+  p.inj_span = plant_span;
+  p.inj_pass = (uint32_t)pass;
+  p.dump_out = d_dump.get();
+  p.dump_pass = (uint32_t)pass;
+  p.guard_vecs = guarded ? kGuardBytes / 16 : 0;
+  p.guard_bad = d_guard.get();
+  hipLaunchKernelGGL(coverage_kernel<true>, dim3(grid_blocks), dim3(kBlock),
+                     (size_t)lds_bytes + (guarded ? kGuardBytes : 0), 0, p);
+  CHECK(hipGetLastError());
+  CHECK(hipDeviceSynchronize());
+  CHECK(hipMemcpy(host_out, d_dump.get(), dump_bytes, hipMemcpyDeviceToHost));
+  CHECK(hipMemcpy(guard_bad_out, d_guard.get(), sizeof(unsigned int), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+void clear_result(CroComputeResult* out) {
   memset(out, 0, sizeof(*out));
   out->first_bad_round = out->first_bad_record = -1;
   out->agg.first_bad_index = -1;
   out->agg.xcd = out->agg.se = out->agg.sh = out->agg.cu = out->agg.simd = -1;
   out->agg.first_bad = ~0u;
+}
+
+}  // namespace
+
+extern "C" int cro_probe_compute_tiles(int device, const struct CroComputeOpts* opts,
+                                       const float* e32, const int* e8, const float* e16,
+                                       struct CroComputeResult* out,
+                                       struct CroCoverageRecord* records_out,
+                                       int max_records) {
+  clear_result(out);
+  CallerTiles tiles;
+  tiles.e32 = e32;
+  tiles.e8 = e8;
+  tiles.e16 = e16;
   const double t0 = now_ms();
-  out->rc = run_compute(device, opts, out, records_out, max_records);
+  out->rc = run_compute(device, opts, tiles, out, records_out, max_records);
   out->t_total_ms = now_ms() - t0;
   return out->rc;
+}
+
+extern "C" int cro_probe_compute_records(int device, const struct CroComputeOpts* opts,
+                                         struct CroComputeResult* out,
+                                         struct CroCoverageRecord* records_out,
+                                         int max_records) {
+  return cro_probe_compute_tiles(device, opts, nullptr, nullptr, nullptr, out, records_out,
+                                 max_records);
+}
+
+extern "C" int cro_probe_compute_lds_dump(int device, int grid_blocks, int lds_bytes,
+                                          unsigned int seed, int pass,
+                                          unsigned int plant_elem, unsigned int plant_span,
+                                          int plant_bit, unsigned int* host_out,
+                                          unsigned int* guard_bad_out) {
+  CroComputeResult res;  // for the HIP error text, which this entry does not return
+  clear_result(&res);
+  return run_lds_dump(device, grid_blocks, lds_bytes, seed, pass, plant_elem, plant_span,
+                      plant_bit, host_out, guard_bad_out, &res);
 }
 
 extern "C" int cro_probe_compute(int device, const struct CroComputeOpts* opts,

@@ -156,12 +156,23 @@ struct CroComputeOpts {
   // bit in its COMPUTED value on the waves whose CU key is selftest_key;
   // exactly those waves may flag it.  For the LDS test, where each word is
   // checked by one wave only, the flip is repeated at the same lane and trip
-  // of all four waves of a workgroup.
+  // of all four waves of a workgroup.  Neither mode makes an LDS word wrong:
+  // for the LDS test both alter a difference already in a register.
+  // Modes 3 and 4 (selftest_test = 3 only) plant in LDS itself: in the passes
+  // selftest_pass names, of every iteration, after the fill's barrier and
+  // before the verify loads, the kernel flips bit selftest_bit of the
+  // selftest_span words from selftest_elem on with real LDS stores, each word
+  // by a thread of another wave than the one that verifies it, then takes a
+  // second barrier.  The verify loop is the clean run's.  Mode 3: on every
+  // workgroup.  Mode 4: on the workgroups whose CU key is selftest_key.  All
+  // stores are in bounds: wrong data only.
   int selftest_mode;
   int selftest_test;
   int selftest_bit;
   unsigned int selftest_elem;
   unsigned int selftest_key;
+  unsigned int selftest_span;  // modes 3, 4: words, >= 1, elem + span <= lds_bytes / 4
+  int selftest_pass;           // modes 3, 4: 0 pattern, 1 complement, 2 both
   double min_cu_fraction;  // 0 = off; else fail when cus_seen / cus_expected is below
 };
 
@@ -190,6 +201,25 @@ int cro_probe_compute(int device, const struct CroComputeOpts* opts,
 int cro_probe_compute_records(int device, const struct CroComputeOpts* opts,
                               struct CroComputeResult* out,
                               struct CroCoverageRecord* records_out, int max_records);
+// The same, with the caller's expected tiles, for tests of the per-wave
+// tallies: each non-null tile (e32 256 floats, e8 256 ints, e16 1024 floats,
+// row-major) stands in for the cached expected tile in this call only.  The
+// kernel is the same; it is handed another pointer.
+int cro_probe_compute_tiles(int device, const struct CroComputeOpts* opts, const float* e32,
+                            const int* e8, const float* e16, struct CroComputeResult* out,
+                            struct CroCoverageRecord* records_out, int max_records);
+// Raw entry for tests of the LDS march: the coverage kernel itself (one
+// iteration, grid_blocks workgroups, at most 8) up to the fill of pass `pass`
+// (0 pattern, 1 complement), its barrier and, with plant_span > 0, a plant as
+// self-test mode 3 makes it (plant_elem, plant_span, plant_bit); then each
+// workgroup copies its LDS to host_out + workgroup * lds_bytes / 4 and
+// returns.  Where lds_bytes <= 163840 - 1024 the launch asks for 1024 bytes
+// more, preset to 0xA5A5A5A5 before the fill: *guard_bad_out = how many of
+// those 256 words per workgroup changed, summed.  -10 = bad argument.
+int cro_probe_compute_lds_dump(int device, int grid_blocks, int lds_bytes, unsigned int seed,
+                               int pass, unsigned int plant_elem, unsigned int plant_span,
+                               int plant_bit, unsigned int* host_out,
+                               unsigned int* guard_bad_out);
 // Raw tile entry for the lane-map tests, one wave of the coverage kernel's
 // body on caller data.  kind 1: i8, A 16xK, B Kx16 (int8), D 16x16 (int32),
 // K a multiple of 64.  kind 2: bf16, A 32xK, B Kx32 (bf16 bit patterns),

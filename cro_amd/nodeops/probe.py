@@ -115,6 +115,8 @@ class CroComputeOpts(ctypes.Structure):
         ("selftest_bit", ctypes.c_int),
         ("selftest_elem", ctypes.c_uint),
         ("selftest_key", ctypes.c_uint),
+        ("selftest_span", ctypes.c_uint),
+        ("selftest_pass", ctypes.c_int),
         ("min_cu_fraction", ctypes.c_double),
     ]
 
@@ -255,6 +257,17 @@ def load_library(required: Optional[bool] = None) -> Optional[ctypes.CDLL]:
         ctypes.POINTER(CroCoverageRecord), ctypes.c_int,
     ]
     lib.cro_probe_compute_records.restype = ctypes.c_int
+    lib.cro_probe_compute_tiles.argtypes = [
+        ctypes.c_int, ctypes.POINTER(CroComputeOpts), ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_void_p, ctypes.POINTER(CroComputeResult), ctypes.POINTER(CroCoverageRecord),
+        ctypes.c_int,
+    ]
+    lib.cro_probe_compute_tiles.restype = ctypes.c_int
+    lib.cro_probe_compute_lds_dump.argtypes = [
+        ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint, ctypes.c_int,
+        ctypes.c_uint, ctypes.c_uint, ctypes.c_int, ctypes.c_void_p, u32p,
+    ]
+    lib.cro_probe_compute_lds_dump.restype = ctypes.c_int
     lib.cro_probe_mfma_tile.argtypes = [
         ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_int,
@@ -585,7 +598,8 @@ def pattern_verify(device: int, seed: int, invert, base_word: int, words) -> dic
 
 def _compute_opts(grid_blocks=0, lds_bytes=0, iters=0, max_rounds=0, seed=0,
                   min_cu_fraction=0.0, selftest_mode=0, selftest_test=0, selftest_elem=0,
-                  selftest_bit=0, selftest_key=0) -> "CroComputeOpts":
+                  selftest_bit=0, selftest_key=0, selftest_span=0,
+                  selftest_pass=0) -> "CroComputeOpts":
     if isinstance(selftest_test, str):
         selftest_test = COMPUTE_TESTS.index(selftest_test)
     return CroComputeOpts(
@@ -593,8 +607,33 @@ def _compute_opts(grid_blocks=0, lds_bytes=0, iters=0, max_rounds=0, seed=0,
         max_rounds=int(max_rounds), seed=int(seed) & 0xFFFFFFFF,
         selftest_mode=int(selftest_mode), selftest_test=int(selftest_test),
         selftest_bit=int(selftest_bit), selftest_elem=int(selftest_elem),
-        selftest_key=int(selftest_key), min_cu_fraction=float(min_cu_fraction),
+        selftest_key=int(selftest_key), selftest_span=int(selftest_span),
+        selftest_pass=int(selftest_pass), min_cu_fraction=float(min_cu_fraction),
     )
+
+
+# expected tiles a caller may hand to run_compute_records: name, dtype, elements
+COMPUTE_TILE_SPECS = (("f32", "float32", 256), ("i8", "int32", 256), ("bf16", "float32", 1024))
+
+
+def _caller_tiles(tiles) -> list:
+    """The three tile arguments of cro_probe_compute_tiles, in the C order:
+    a contiguous array of the tile's own type and size, or None."""
+    import numpy as np
+
+    tiles = dict(tiles or {})
+    out = []
+    for name, dtype, elems in COMPUTE_TILE_SPECS:
+        tile = tiles.pop(name, None)
+        if tile is not None:
+            tile = np.asarray(tile)
+            if tile.dtype != np.dtype(dtype) or tile.size != elems:
+                raise ValueError(f"{name} tile wants {elems} values of {dtype}")
+            tile = np.ascontiguousarray(tile).reshape(-1)
+        out.append(tile)
+    if tiles:
+        raise ValueError(f"unknown tiles: {sorted(tiles)}")
+    return out
 
 
 def run_compute(device: int = 0, **opts) -> dict:
@@ -611,13 +650,17 @@ def run_compute(device: int = 0, **opts) -> dict:
     return _result_dict(res, rc)
 
 
-def run_compute_records(device: int = 0, **opts):
+def run_compute_records(device: int = 0, tiles=None, **opts):
     """As run_compute, and returns the raw per-wave records as well: a
-    structured numpy array of rounds * grid_blocks * 4 records, round-major."""
+    structured numpy array of rounds * grid_blocks * 4 records, round-major.
+    ``tiles`` (for tests): a dict with any of ``"f32"`` (256 float32), ``"i8"``
+    (256 int32) and ``"bf16"`` (1024 float32), each taking the place of that
+    test's expected tile in this call only."""
     import numpy as np
 
     lib = load_library(required=True)
     c_opts = _compute_opts(**opts)
+    c_tiles = _caller_tiles(tiles)
     res = CroComputeResult()
     # room for what was asked; a default grid is one workgroup per CU, and
     # no device of this family has more than 1024 of them
@@ -625,12 +668,57 @@ def run_compute_records(device: int = 0, **opts):
     rounds = c_opts.max_rounds or 4
     cap = max(blocks * 4 * rounds, 1)
     buf = (CroCoverageRecord * cap)()
-    rc = lib.cro_probe_compute_records(device, ctypes.byref(c_opts), ctypes.byref(res), buf, cap)
+    rc = lib.cro_probe_compute_tiles(
+        device, ctypes.byref(c_opts), *[t.ctypes.data if t is not None else None for t in c_tiles],
+        ctypes.byref(res), buf, cap,
+    )
     out = _result_dict(res, rc)
     n = min(out["rounds"] * out["grid_blocks"] * 4, cap)
     dtype = np.dtype([(name, np.uint32) for name, _ in CroCoverageRecord._fields_])
     records = np.frombuffer(buf, dtype=dtype, count=cap)[:n].copy()
     return out, records
+
+
+def compute_lds_dump(device: int, grid_blocks: int, lds_bytes: int, seed: int = 0, invert=0,
+                     plant_elem: int = 0, plant_span: int = 0, plant_bit: int = 0):
+    """What the coverage kernel's march wrote (for tests): each workgroup's LDS
+    after the fill of the pattern (``invert`` 0) or complement pass and, with
+    ``plant_span`` > 0, a plant as self-test mode 3 makes it.  Returns a uint32
+    array of grid_blocks x lds_bytes / 4 words and how many guard words after
+    the marched ones changed (always 0 where the size leaves no room for a
+    guard, above 163840 - 1024 bytes)."""
+    import numpy as np
+
+    lib = load_library(required=True)
+    words = np.zeros((max(int(grid_blocks), 0), max(int(lds_bytes), 0) // 4), dtype=np.uint32)
+    guard_bad = ctypes.c_uint(0)
+    rc = lib.cro_probe_compute_lds_dump(
+        device, int(grid_blocks), int(lds_bytes), int(seed) & 0xFFFFFFFF, 1 if invert else 0,
+        int(plant_elem), int(plant_span), int(plant_bit), words.ctypes.data,
+        ctypes.byref(guard_bad),
+    )
+    if rc != 0:
+        raise RuntimeError(f"cro_probe_compute_lds_dump failed: rc={rc}")
+    return words, guard_bad.value
+
+
+def lds_verify_wave(word):
+    """The wave of a workgroup that verifies LDS word ``word`` in the coverage
+    kernel's march: 16-byte vector v = word // 4 is checked by thread v % 256,
+    that is wave (v // 64) % 4.  int or numpy array."""
+    return ((word // 4) // 64) % 4
+
+
+def lds_plant_per_wave(elem: int, span: int):
+    """For a plant of ``span`` words from ``elem`` on: per wave 0..3 how many of
+    them it verifies and the lowest (0xFFFFFFFF where it verifies none)."""
+    import numpy as np
+
+    words = np.arange(elem, elem + span, dtype=np.int64)
+    owner = lds_verify_wave(words)
+    counts = [int((owner == w).sum()) for w in range(4)]
+    firsts = [int(words[owner == w].min()) if counts[w] else 0xFFFFFFFF for w in range(4)]
+    return counts, firsts
 
 
 MFMA_TILE_KINDS = {"i8": 1, "bf16": 2}

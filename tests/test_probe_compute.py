@@ -567,6 +567,146 @@ def test_run_compute_names_tests_and_builds_opts():
     assert (opts.selftest_bit, opts.selftest_key) == (30, 0x54700)
     zero = probe_mod._compute_opts()
     assert bytes(zero) == bytes(ctypes.sizeof(zero))  # every default is 0
+    plant = probe_mod._compute_opts(selftest_mode=3, selftest_test="lds", selftest_elem=1023,
+                                    selftest_span=2, selftest_pass=2, selftest_bit=31)
+    assert (plant.selftest_mode, plant.selftest_test, plant.selftest_elem) == (3, 3, 1023)
+    assert (plant.selftest_span, plant.selftest_pass, plant.selftest_bit) == (2, 2, 31)
+    assert probe_mod._compute_opts(selftest_span=0xFFFFFFFF).selftest_span == 0xFFFFFFFF
+
+
+def test_plant_fields_sit_between_the_key_and_the_floor():
+    """The two new options fill the eight bytes before min_cu_fraction: no
+    padding appears, and every older field keeps its offset."""
+    opts = probe_mod.CroComputeOpts
+    assert (opts.selftest_key.offset, opts.selftest_span.offset, opts.selftest_pass.offset,
+            opts.min_cu_fraction.offset, ctypes.sizeof(opts)) == (36, 40, 44, 48, 56)
+
+
+class FakeProbeLib:
+    """Records what the wrappers hand to the library's test entries."""
+
+    def __init__(self):
+        self.calls = []
+
+    def cro_probe_compute_tiles(self, device, opts, e32, e8, e16, res, buf, cap):
+        self.calls.append(("tiles", device, opts._obj, (e32, e8, e16), cap))
+        res._obj.rounds, res._obj.grid_blocks, res._obj.ok = 2, 3, 1
+        for i in range(min(2 * 3 * 4, cap)):
+            buf[i].valid, buf[i].first_bad = 1, i
+        return 0
+
+    def cro_probe_compute_lds_dump(self, device, grid, lds_bytes, seed, invert, elem, span, bit,
+                                   out, guard):
+        self.calls.append(("dump", device, grid, lds_bytes, seed, invert, elem, span, bit))
+        words = (ctypes.c_uint * (grid * lds_bytes // 4)).from_address(out)
+        for i in range(len(words)):
+            words[i] = 7 * i
+        guard._obj.value = 5
+        return self.rc
+
+    rc = 0
+
+
+def test_run_compute_records_hands_on_the_callers_tiles(monkeypatch):
+    fake = FakeProbeLib()
+    monkeypatch.setattr(probe_mod, "load_library", lambda required=None: fake)
+    e8 = np.arange(256, dtype=np.int32).reshape(16, 16)
+    e16 = np.arange(1024, dtype=np.float32).reshape(32, 32)
+    res, records = probe_mod.run_compute_records(2, tiles={"i8": e8, "bf16": e16},
+                                                 grid_blocks=3, max_rounds=2, seed=9)
+    (name, device, opts, tiles, cap), = fake.calls
+    assert (name, device, cap) == ("tiles", 2, 3 * 4 * 2)
+    assert (opts.grid_blocks, opts.max_rounds, opts.seed) == (3, 2, 9)
+    assert tiles[0] is None  # f32: the cached tile
+    assert np.array_equal(np.ctypeslib.as_array((ctypes.c_int * 256).from_address(tiles[1])),
+                          e8.ravel())
+    assert np.array_equal(np.ctypeslib.as_array((ctypes.c_float * 1024).from_address(tiles[2])),
+                          e16.ravel())
+    assert res["rounds"] == 2 and len(records) == 24
+    assert records["first_bad"].tolist() == list(range(24))
+    # no tiles: three null pointers
+    probe_mod.run_compute_records(0, grid_blocks=1)
+    assert fake.calls[-1][3] == (None, None, None)
+    # a tile of the wrong type or size never reaches the library
+    for bad in ({"f32": e8}, {"i8": e8[:8]}, {"bf16": e16.astype(np.float64)}, {"f16": e16}):
+        with pytest.raises(ValueError):
+            probe_mod.run_compute_records(0, tiles=bad)
+    assert len(fake.calls) == 2
+
+
+def test_compute_lds_dump_builds_its_arguments(monkeypatch):
+    fake = FakeProbeLib()
+    monkeypatch.setattr(probe_mod, "load_library", lambda required=None: fake)
+    words, guard_bad = probe_mod.compute_lds_dump(1, 3, 1024, seed=-1, invert=True, plant_elem=2,
+                                                  plant_span=5, plant_bit=7)
+    assert fake.calls == [("dump", 1, 3, 1024, 0xFFFFFFFF, 1, 2, 5, 7)]
+    assert words.shape == (3, 256) and words.dtype == np.uint32 and guard_bad == 5
+    assert np.array_equal(words.ravel(), 7 * np.arange(768))  # block-major
+    probe_mod.compute_lds_dump(0, 1, 16)
+    assert fake.calls[-1] == ("dump", 0, 1, 16, 0, 0, 0, 0, 0)
+    fake.rc = -10
+    with pytest.raises(RuntimeError, match="rc=-10"):
+        probe_mod.compute_lds_dump(0, 1, 16)
+
+
+# -- which wave verifies which LDS word -----------------------------------------------------
+
+
+def _walk_verify(lds_words):
+    """The kernel's verify loop, index for index (coverage.hip): the wave that
+    loads each word, and how often each word is loaded."""
+    n4 = lds_words >> 2
+    owner = np.full(lds_words, -1)
+    loads = np.zeros(lds_words, dtype=int)
+    for tid in range(256):
+        lane, wave = tid & 63, tid >> 6
+        v0 = tid - lane
+        while v0 < n4:
+            v = v0 + lane
+            if v < n4:
+                owner[4 * v:4 * v + 4] = wave
+                loads[4 * v:4 * v + 4] += 1
+            v0 += 256
+    return owner, loads
+
+
+def _walk_plant(lds_words, elem, span):
+    """The kernel's plant loop: for each word stored, the storing thread."""
+    lo, hi = elem, elem + span
+    stores = {}
+    for tid in range(256):
+        v = ((lo >> 2) & ~255) | (tid ^ 128)
+        while (v << 2) < hi:
+            for w in range(v << 2, (v << 2) + 4):
+                if lo <= w < hi:
+                    assert w not in stores and w < lds_words
+                    stores[w] = tid
+            v += 256
+    return stores
+
+
+@pytest.mark.parametrize("lds_bytes", [16, 1024, 4096 + 16, 163840])
+def test_lds_wave_expectations_agree_with_a_walk_of_the_kernels_loops(lds_bytes):
+    lds_words = lds_bytes // 4
+    owner, loads = _walk_verify(lds_words)
+    assert np.all(loads == 1)  # every word verified, once
+    assert np.array_equal(owner, probe_mod.lds_verify_wave(np.arange(lds_words)))
+    plants = [(0, 1), (lds_words - 1, 1), (0, lds_words)]
+    plants += [(e, 2) for e in (3, 255, 1023) if e + 2 <= lds_words]
+    plants += [(2, 5)] if lds_words >= 7 else []
+    for elem, span in plants:
+        counts, firsts = probe_mod.lds_plant_per_wave(elem, span)
+        words = np.arange(elem, elem + span)
+        for wave in range(4):
+            mine = words[owner[words] == wave]
+            assert counts[wave] == mine.size, (elem, span, wave)
+            assert firsts[wave] == (mine.min() if mine.size else NONE32), (elem, span, wave)
+        # each planted word is stored once, in bounds, by a thread of another
+        # wave than the one that verifies it
+        stores = _walk_plant(lds_words, elem, span)
+        assert sorted(stores) == words.tolist(), (elem, span)
+        for w, tid in stores.items():
+            assert tid >> 6 != owner[w], (elem, span, w)
 
 
 # -- probe_via_exec -----------------------------------------------------------------------
