@@ -20,6 +20,9 @@
 //                                            (libcroscrub.so, loaded at run time)
 //       [--lds [--lds-min-cu-fraction X]]    + clear and verify every CU's LDS
 //                                            (libcroldsscrub.so, loaded at run time)
+//       [--regs [--regs-min-simd-fraction X]]  + clear and verify every SIMD's
+//                                            vector registers
+//                                            (libcroregscrub.so, loaded at run time)
 //   croagent drain  --bdf 0000:5a:00.0       sysfs PCI remove
 //   croagent rescan                          sysfs PCI rescan
 //
@@ -32,6 +35,7 @@
 
 #include "../hip/croprobe.h"
 #include "../hip/croldsscrub.h"
+#include "../hip/croregscrub.h"
 #include "../hip/croscrub.h"
 
 #include <cinttypes>
@@ -414,15 +418,45 @@ void print_lds_scrub(const CroLdsScrubResult& r) {
          json_escape(r.msg).c_str());
 }
 
-// The result as one JSON object, keys as nodeops/scrub.py run_scrub.  With the
-// LDS scrub's result it is nested under "lds" and merged as nodeops/scrub.py
-// merge_lds_result does: ok only if both passed; rc and msg are the VRAM
-// scrub's when that failed, else the LDS scrub's.  Returns the merged ok.
-bool print_scrub(const CroScrubResult& r, const CroLdsScrubResult* lds) {
+// The register scrub's result as one JSON object, keys as nodeops/regscrub.py
+// run_reg_scrub.
+void print_reg_scrub(const CroRegScrubResult& r) {
+  printf("{\"ok\":%s,\"rc\":%d,\"simds_expected\":%d,\"simds_seen\":%d,\"cus_seen\":%d,"
+         "\"xcds_seen\":%d,\"rounds\":%d,\"grid\":%d,\"first_vgpr\":%d,"
+         "\"regs_per_lane\":%d,\"waves\":%llu,\"bytes_scrubbed\":%llu,"
+         "\"dirty_words_before\":%llu,\"dirty_waves\":%llu,",
+         r.ok && r.rc == 0 ? "true" : "false", r.rc, r.simds_expected, r.simds_seen, r.cus_seen,
+         r.xcds_seen, r.rounds, r.grid, r.first_vgpr, r.regs_per_lane, r.waves,
+         r.bytes_scrubbed, r.dirty_words_before, r.dirty_waves);
+  printf("\"n_bad\":%llu,\"recheck_dirty_words\":%llu,\"first_dirty_word\":%u,"
+         "\"first_bad_word\":%u,\"bits_bad\":%u,\"bad_waves\":%d,\"xcd\":%d,\"se\":%d,"
+         "\"sh\":%d,\"cu\":%d,\"simd\":%d,\"wave\":%d,\"gpu_ms\":%.3f,"
+         "\"t_total_ms\":%.1f,\"msg\":\"%s\"}",
+         r.n_bad, r.recheck_dirty_words, r.first_dirty_word, r.first_bad_word, r.bits_bad,
+         r.bad_waves, r.xcd, r.se, r.sh, r.cu, r.simd, r.wave, r.gpu_ms, r.t_total_ms,
+         json_escape(r.msg).c_str());
+}
+
+// The result as one JSON object, keys as nodeops/scrub.py run_scrub.  The LDS
+// scrub's result is nested under "lds" and the register scrub's under "regs"
+// after it, merged as nodeops/scrub.py merge_lds_result and merge_regs_result
+// do: ok only if every stage passed; rc and msg are those of the first stage
+// that failed, else the last stage's.  Returns the merged ok.
+bool print_scrub(const CroScrubResult& r, const CroLdsScrubResult* lds,
+                 const CroRegScrubResult* regs) {
   const bool vram_ok = r.ok && r.rc == 0;
-  const bool ok = vram_ok && (lds == nullptr || (lds->ok && lds->rc == 0));
-  const int rc = vram_ok && lds ? lds->rc : r.rc;
-  const char* msg = vram_ok && lds ? lds->msg : r.msg;
+  const bool lds_ok = lds == nullptr || (lds->ok && lds->rc == 0);
+  const bool ok = vram_ok && lds_ok && (regs == nullptr || (regs->ok && regs->rc == 0));
+  int rc = r.rc;
+  const char* msg = r.msg;
+  if (vram_ok && lds) {
+    rc = lds->rc;
+    msg = lds->msg;
+  }
+  if (vram_ok && lds_ok && regs) {
+    rc = regs->rc;
+    msg = regs->msg;
+  }
   printf("{\"ok\":%s,\"rc\":%d,\"vram_total\":%lld,\"vram_free_before\":%lld,"
          "\"bytes_target\":%lld,\"bytes_scrubbed\":%lld,\"bytes_verified\":%lld,"
          "\"chunks\":%d,\"alloc_refusals\":%d,\"dirty_words_before\":%llu,",
@@ -437,6 +471,10 @@ bool print_scrub(const CroScrubResult& r, const CroLdsScrubResult* lds) {
   if (lds) {
     printf(",\"lds\":");
     print_lds_scrub(*lds);
+  }
+  if (regs) {
+    printf(",\"regs\":");
+    print_reg_scrub(*regs);
   }
   printf("}\n");
   return ok;
@@ -457,11 +495,13 @@ void* load_entry(const char* soname, const char* symbol, std::string* why) {
   return entry;
 }
 
-// Both libraries are looked up before anything runs: a scrub that was asked
-// to cover LDS and cannot says so and scrubs nothing.
-int cmd_scrub(int device, const CroScrubOpts& opts, const CroLdsScrubOpts* lds_opts) {
+// Every library is looked up before anything runs: a scrub that was asked to
+// cover LDS or the registers and cannot says so and scrubs nothing.
+int cmd_scrub(int device, const CroScrubOpts& opts, const CroLdsScrubOpts* lds_opts,
+              const CroRegScrubOpts* reg_opts) {
   typedef int (*ScrubRun)(int, const CroScrubOpts*, CroScrubResult*);
   typedef int (*LdsScrubRun)(int, const CroLdsScrubOpts*, CroLdsScrubResult*);
+  typedef int (*RegScrubRun)(int, const CroRegScrubOpts*, CroRegScrubResult*);
   std::string why;
   const ScrubRun run = (ScrubRun)load_entry("libcroscrub.so", "cro_scrub_run", &why);
   if (run == nullptr) return scrub_unavailable(why);
@@ -470,11 +510,19 @@ int cmd_scrub(int device, const CroScrubOpts& opts, const CroLdsScrubOpts* lds_o
     run_lds = (LdsScrubRun)load_entry("libcroldsscrub.so", "cro_lds_scrub_run", &why);
     if (run_lds == nullptr) return scrub_unavailable(why);
   }
+  RegScrubRun run_regs = nullptr;
+  if (reg_opts) {
+    run_regs = (RegScrubRun)load_entry("libcroregscrub.so", "cro_reg_scrub_run", &why);
+    if (run_regs == nullptr) return scrub_unavailable(why);
+  }
   CroScrubResult result;
   run(device, &opts, &result);
   CroLdsScrubResult lds_result;
   if (run_lds) run_lds(device, lds_opts, &lds_result);
-  return print_scrub(result, run_lds ? &lds_result : nullptr) ? 0 : 1;
+  CroRegScrubResult reg_result;
+  if (run_regs) run_regs(device, reg_opts, &reg_result);
+  return print_scrub(result, run_lds ? &lds_result : nullptr,
+                     run_regs ? &reg_result : nullptr) ? 0 : 1;
 }
 
 }  // namespace
@@ -498,6 +546,9 @@ int main(int argc, char** argv) {
   bool lds = false;
   CroLdsScrubOpts lds_opts;  // nor here
   memset(&lds_opts, 0, sizeof(lds_opts));
+  bool regs = false;
+  CroRegScrubOpts reg_opts;  // nor here
+  memset(&reg_opts, 0, sizeof(reg_opts));
   for (int i = 2; i < argc; ++i) {
     std::string arg = argv[i];
     if (arg == "--sysroot" && i + 1 < argc) g_sysroot = argv[++i];
@@ -515,6 +566,8 @@ int main(int argc, char** argv) {
     else if (arg == "--min-fraction" && i + 1 < argc) scrub_opts.min_fraction = atof(argv[++i]);
     else if (arg == "--lds") lds = true;
     else if (arg == "--lds-min-cu-fraction" && i + 1 < argc) lds_opts.min_cu_fraction = atof(argv[++i]);
+    else if (arg == "--regs") regs = true;
+    else if (arg == "--regs-min-simd-fraction" && i + 1 < argc) reg_opts.min_simd_fraction = atof(argv[++i]);
   }
   if (cmd == "list") return cmd_list();
   if (cmd == "cxl") return cmd_cxl();
@@ -538,7 +591,7 @@ int main(int argc, char** argv) {
       device = resolve_device_by_bdf(lower);
       if (device < 0) return scrub_unavailable("no HIP device with bdf " + bdf);
     }
-    return cmd_scrub(device, scrub_opts, lds ? &lds_opts : nullptr);
+    return cmd_scrub(device, scrub_opts, lds ? &lds_opts : nullptr, regs ? &reg_opts : nullptr);
   }
   if (cmd == "drain") return cmd_drain(bdf);
   if (cmd == "rescan") return cmd_rescan();

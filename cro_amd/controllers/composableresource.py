@@ -218,8 +218,9 @@ class ComposableResourceReconciler(Reconciler):
 
     def _scrub_before_drain(self, resource: ComposableResource, ops) -> None:
         """Overwrite and verify the device's VRAM (and, where the scrub hook
-        covers it, every CU's LDS: the result then has an "lds" object) before
-        it leaves the node, once per detach.  A scrub that does not pass keeps
+        covers them, every CU's LDS and every SIMD's vector registers: the
+        result then has an "lds" and a "regs" object) before it leaves the
+        node, once per detach.  A scrub that does not pass keeps
         the device here (ScrubFailed) unless the detach is forced."""
         uid = resource.metadata.uid
         if self._scrub_done.get(uid):
@@ -241,6 +242,7 @@ class ComposableResourceReconciler(Reconciler):
         self.metrics.scrub_bytes_total.inc(scrubbed)
         fraction = float(result.get("fraction", 0.0) or 0.0)
         lds = result.get("lds") if isinstance(result.get("lds"), dict) else None
+        regs = result.get("regs") if isinstance(result.get("regs"), dict) else None
         if result.get("ok"):
             self._scrub_done[uid] = True
             lds_clause = ""
@@ -251,17 +253,27 @@ class ComposableResourceReconciler(Reconciler):
                     f"({int(lds.get('bytes_scrubbed', 0) or 0) // 1024} KiB), "
                     f"{int(lds.get('dirty_words_before', 0) or 0)} dirty LDS words found before"
                 )
+            regs_clause = ""
+            if regs is not None:
+                regs_clause = (
+                    f"; vector registers of {int(regs.get('simds_seen', 0) or 0)} of "
+                    f"{int(regs.get('simds_expected', 0) or 0)} SIMDs cleared "
+                    f"({int(regs.get('bytes_scrubbed', 0) or 0) // 1024} KiB), "
+                    f"{int(regs.get('dirty_words_before', 0) or 0)} dirty register words "
+                    "found before"
+                )
             self.recorder.normal(
                 resource,
                 "Scrubbed",
                 f"scrubbed {scrubbed / 2**30:.2f} GiB ({100.0 * fraction:.1f} % of VRAM) "
                 f"of device {device_id}, verified; "
                 f"{int(result.get('dirty_words_before', 0) or 0)} dirty words found before; "
-                f"{float(result.get('t_total_ms', 0.0) or 0.0):.0f} ms" + lds_clause,
+                f"{float(result.get('t_total_ms', 0.0) or 0.0):.0f} ms" + lds_clause + regs_clause,
             )
             return
         reason = {
             -40: "residue", -41: "fraction", -42: "lds_residue", -43: "lds_coverage",
+            -44: "reg_residue", -45: "reg_coverage",
         }.get(result.get("rc"), "error")
         self.metrics.scrub_failures_total.labels(reason=reason).inc()
         # lead with what an operator acts on, before the scrub's own message
@@ -275,6 +287,19 @@ class ComposableResourceReconciler(Reconciler):
                 f"n_bad={where.get('n_bad')} "
                 f"recheck_dirty_words={where.get('recheck_dirty_words')} "
                 f"cus_seen={where.get('cus_seen')}/{where.get('cus_expected')}: "
+                f"{result.get('msg', '')}"
+            )
+        elif reason in ("reg_residue", "reg_coverage"):
+            where = regs if regs is not None else result
+            msg = (
+                f"scrub of device {device_id} failed: {reason} "
+                f"xcd={where.get('xcd')} se={where.get('se')} sh={where.get('sh')} "
+                f"cu={where.get('cu')} simd={where.get('simd')} wave={where.get('wave')} "
+                f"first_bad_word={where.get('first_bad_word')} "
+                f"bits_bad=0x{int(where.get('bits_bad', 0) or 0):08x} "
+                f"n_bad={where.get('n_bad')} "
+                f"recheck_dirty_words={where.get('recheck_dirty_words')} "
+                f"simds_seen={where.get('simds_seen')}/{where.get('simds_expected')}: "
                 f"{result.get('msg', '')}"
             )
         else:

@@ -52,6 +52,15 @@ LDS_SCRUB_HEADERS = [
     COVERAGE_HEADER,  # for cro_cov_cu_key and cro_cov_decode
 ]
 LDS_SCRUB_OUT = os.path.join(HIP_DIR, "libcroldsscrub.so")
+# register scrub stage: a library of its own once more (the LDS scrub
+# library's list above is pinned by its tests too)
+REG_SCRUB_SRC = os.path.join(HIP_DIR, "regscrub.hip")
+REG_SCRUB_HEADERS = [
+    os.path.join(HIP_DIR, "croregscrub.h"),
+    os.path.join(HIP_DIR, "crohost.h"),
+    COVERAGE_HEADER,  # for cro_cov_decode
+]
+REG_SCRUB_OUT = os.path.join(HIP_DIR, "libcroregscrub.so")
 AGENT_SRC = os.path.join(AGENT_DIR, "croagent.cpp")
 AGENT_OUT = os.path.join(AGENT_DIR, "croagent")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -98,11 +107,21 @@ def build_lds_scrub(force: bool = False) -> str:
     return LDS_SCRUB_OUT
 
 
+def build_reg_scrub(force: bool = False) -> str:
+    """libcroregscrub.so: the register scrub stage (regscrub.hip)."""
+    if force or _stale(REG_SCRUB_OUT, [REG_SCRUB_SRC] + REG_SCRUB_HEADERS):
+        subprocess.run(
+            [HIPCC, *DEVICE_FLAGS, "-fPIC", "-shared", REG_SCRUB_SRC, "-o", REG_SCRUB_OUT],
+            check=True,
+        )
+    return REG_SCRUB_OUT
+
+
 def build_agent(force: bool = False) -> str:
     """croagent: the native node-agent CLI (links libcroprobe; loads
-    libcroscrub.so and libcroldsscrub.so at run time, so those libraries are
-    no inputs here, and neither are croscrub.h and croldsscrub.h, which the
-    agent includes: the input list below is pinned by
+    libcroscrub.so, libcroldsscrub.so and libcroregscrub.so at run time, so
+    those libraries are no inputs here, and neither are croscrub.h,
+    croldsscrub.h and croregscrub.h, which the agent includes: the input list below is pinned by
     tests/test_probe_compute.py.  A --force build, which is what `make build`
     does, picks up a change of those headers)."""
     if not force and not _stale(AGENT_OUT, [AGENT_SRC, HEADERS[0], COVERAGE_HEADER, OUT]):
@@ -131,3 +150,4 @@ if __name__ == "__main__":
     print(AGENT_OUT)
     print(build_scrub(force="--force" in sys.argv))
     print(build_lds_scrub(force="--force" in sys.argv))
+    print(build_reg_scrub(force="--force" in sys.argv))

@@ -12,7 +12,9 @@
 //   - this process's own cached probe buffers (they hold probe patterns);
 //   - LDS: that is a stage of its own (ldsscrub.hip, croldsscrub.h), which the
 //     operator runs after this one when --scrub-lds is on;
-//   - registers: no stage covers them.
+//   - the vector registers: a stage of its own too (regscrub.hip,
+//     croregscrub.h), run last when --scrub-regs is on;
+//   - SGPRs and the hardware state registers: no stage covers them.
 // `fraction` is how a site sees the covered share of the device's VRAM.
 //
 // Plain C: nodeops/scrub.py mirrors both structs with ctypes (keep field

@@ -87,7 +87,9 @@ class Metrics:
             "still differ after the fill; fraction: less of the VRAM covered "
             "than the floor asks; lds_residue: LDS words still differ after "
             "the fill or at the recheck; lds_coverage: fewer CUs reached than "
-            "the floor asks; error: the scrub could not run)",
+            "the floor asks; reg_residue: vector register words still differ "
+            "after the fill or at the recheck; reg_coverage: fewer SIMDs "
+            "reached than the floor asks; error: the scrub could not run)",
             ["reason"],
         )
         self.scrub_seconds = Histogram(

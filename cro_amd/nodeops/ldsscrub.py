@@ -3,8 +3,9 @@ libcroldsscrub.so): clear and verify every CU's LDS before a GPU is drained.
 
 Fails LOUDLY on a GPU node without the compiled library, as the VRAM scrub's
 wrapper does: a site that asked for the LDS scrub must never detach without
-it and not hear of it.  What the stage covers and what it does not (registers)
-is in cro_amd/hip/croldsscrub.h.
+it and not hear of it.  What the stage covers and what it does not (registers:
+the vector registers are nodeops/regscrub.py's stage) is in
+cro_amd/hip/croldsscrub.h.
 """
 
 from __future__ import annotations

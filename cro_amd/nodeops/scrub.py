@@ -209,11 +209,28 @@ def merge_lds_result(vram: dict, lds: dict) -> dict:
     return out
 
 
+def merge_regs_result(merged: dict, regs: dict) -> dict:
+    """``merged`` (the VRAM scrub's result, the LDS scrub's already merged in
+    when that ran) with the register scrub's nested under ``"regs"``, after
+    ``"lds"``: ``ok`` only if every stage passed; ``rc`` and ``msg`` stay those
+    of the first stage that failed, else become the register scrub's."""
+    out = dict(merged)
+    out["regs"] = regs
+    out["ok"] = bool(merged.get("ok")) and bool(regs.get("ok"))
+    if merged.get("ok"):
+        out["rc"] = regs.get("rc")
+        out["msg"] = regs.get("msg", "")
+    return out
+
+
 def make_scrub_fn(max_bytes: int = 0, reserve_bytes: int = 0, min_fraction: float = 0.0,
-                  lds: bool = False, lds_min_cu_fraction: float = 0.0):
+                  lds: bool = False, lds_min_cu_fraction: float = 0.0, regs: bool = False,
+                  regs_min_simd_fraction: float = 0.0):
     """AmdNodeOps scrub hook: GPUDevice → scrub result on the right ordinal.
     ``lds``: the LDS scrub (nodeops/ldsscrub.py) runs after the VRAM scrub and
-    its result is merged in (merge_lds_result)."""
+    its result is merged in (merge_lds_result).  ``regs``: the register scrub
+    (nodeops/regscrub.py) runs after those and is merged in last
+    (merge_regs_result)."""
 
     def scrub(gpu) -> dict:
         dev = hip_device_for_bdf(gpu.pci_bdf)
@@ -221,22 +238,28 @@ def make_scrub_fn(max_bytes: int = 0, reserve_bytes: int = 0, min_fraction: floa
             dev = 0
         result = run_scrub(dev, max_bytes=max_bytes, reserve_bytes=reserve_bytes,
                            min_fraction=min_fraction)
-        if not lds:
-            return result
-        from . import ldsscrub
+        if lds:
+            from . import ldsscrub
 
-        return merge_lds_result(
-            result, ldsscrub.run_lds_scrub(dev, min_cu_fraction=lds_min_cu_fraction))
+            result = merge_lds_result(
+                result, ldsscrub.run_lds_scrub(dev, min_cu_fraction=lds_min_cu_fraction))
+        if regs:
+            from . import regscrub
+
+            result = merge_regs_result(
+                result, regscrub.run_reg_scrub(dev, min_simd_fraction=regs_min_simd_fraction))
+        return result
 
     return scrub
 
 
 def scrub_via_exec(execer, node: str, gpu, argv_prefix=None, max_mib=None, reserve_mib=None,
-                   min_fraction=0, lds=False, lds_min_cu_fraction=0.0) -> dict:
+                   min_fraction=0, lds=False, lds_min_cu_fraction=0.0, regs=False,
+                   regs_min_simd_fraction=0.0) -> dict:
     """Scrub through the node agent (``croagent scrub --bdf``), for
     controllers that run off-node.  Returns the same dict shape as run_scrub
-    (with ``lds``: as make_scrub_fn's, merged by the agent); ``argv_prefix`` as
-    in probe.probe_via_exec."""
+    (with ``lds`` and ``regs``: as make_scrub_fn's, merged by the agent);
+    ``argv_prefix`` as in probe.probe_via_exec."""
     import json as _json
 
     argv = list(argv_prefix or []) + ["croagent", "scrub", "--bdf", gpu.pci_bdf]
@@ -250,6 +273,10 @@ def scrub_via_exec(execer, node: str, gpu, argv_prefix=None, max_mib=None, reser
         argv += ["--lds"]
         if lds_min_cu_fraction:
             argv += ["--lds-min-cu-fraction", str(float(lds_min_cu_fraction))]
+    if regs:
+        argv += ["--regs"]
+        if regs_min_simd_fraction:
+            argv += ["--regs-min-simd-fraction", str(float(regs_min_simd_fraction))]
     rc, out, err = execer.run(node, argv, timeout=300)
     if not out.strip():
         return {"ok": False, "rc": rc, "msg": err.strip() or "croagent scrub failed"}
@@ -263,17 +290,21 @@ def scrub_via_exec(execer, node: str, gpu, argv_prefix=None, max_mib=None, reser
 
 
 def make_exec_scrub_fn(execer, node: str, argv_prefix_fn=None, max_mib=None, reserve_mib=None,
-                       min_fraction=0, lds=False, lds_min_cu_fraction=0.0):
+                       min_fraction=0, lds=False, lds_min_cu_fraction=0.0, regs=False,
+                       regs_min_simd_fraction=0.0):
     """AmdNodeOps scrub hook bound to a NodeExec (local or remote agent);
     ``argv_prefix_fn`` as in probe.make_exec_probe_fn."""
 
     def scrub(gpu):
         prefix = argv_prefix_fn() if argv_prefix_fn else None
-        if not lds:
-            return scrub_via_exec(execer, node, gpu, argv_prefix=prefix, max_mib=max_mib,
-                                  reserve_mib=reserve_mib, min_fraction=min_fraction)
+        # a stage that is off passes no keyword of its own: the call is then
+        # exactly what it was before the stage existed
+        stages = {}
+        if lds:
+            stages.update(lds=True, lds_min_cu_fraction=lds_min_cu_fraction)
+        if regs:
+            stages.update(regs=True, regs_min_simd_fraction=regs_min_simd_fraction)
         return scrub_via_exec(execer, node, gpu, argv_prefix=prefix, max_mib=max_mib,
-                              reserve_mib=reserve_mib, min_fraction=min_fraction, lds=True,
-                              lds_min_cu_fraction=lds_min_cu_fraction)
+                              reserve_mib=reserve_mib, min_fraction=min_fraction, **stages)
 
     return scrub
