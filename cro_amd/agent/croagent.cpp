@@ -14,6 +14,8 @@
 //       [--deep [--vram-mib N] [--link-mib N] [--link-floor-gbps X]]
 //                                            + VRAM / host-link data integrity
 //       [--compute [--compute-min-cu-fraction X]]
+//       [--formats [--formats-min-cu-fraction X]]  + the matrix-format stage
+//                                            (libcroformats.so, loaded at run time)
 //                                            + exact checks on every CU and SIMD
 //   croagent scrub  [--device N | --bdf B]   overwrite and verify VRAM before drain
 //       [--max-mib N] [--reserve-mib N] [--min-fraction X]
@@ -35,6 +37,7 @@
 
 #include "../hip/croprobe.h"
 #include "../hip/croldsscrub.h"
+#include "../hip/croformats.h"
 #include "../hip/croregscrub.h"
 #include "../hip/croscrub.h"
 
@@ -331,16 +334,49 @@ void print_compute(const CroComputeResult& r) {
          r.t_total_ms, r.failed_test, r.msg);
 }
 
+// The matrix-format stage's result, keys as nodeops/formats.py run_formats.
+void print_formats(const CroFormatsResult& r) {
+  const CroFormatsAgg& a = r.agg;
+  printf("\"formats\":{\"ok\":%s,\"rc\":%d,\"cus_expected\":%d,\"rounds\":%d,"
+         "\"waves_run\":%llu,\"waves_bad\":%llu,",
+         r.ok ? "true" : "false", r.rc, r.cus_expected, r.rounds, a.waves_run, a.waves_bad);
+  for (int t = 0; t < CRO_FMT_TESTS; ++t)
+    printf("\"bad_%s\":%llu,", cro_fmt_test(t)->name, a.bad[t]);
+  printf("\"first_bad_index\":%lld,\"cus_seen\":%d,\"xcds_seen\":%d,\"simds_seen\":%d,"
+         "\"cus_bad\":%d,\"xcd\":%d,\"se\":%d,\"sh\":%d,\"cu\":%d,\"simd\":%d,"
+         "\"first_fail_mask\":%u,\"n_bad\":%u,\"first_bad\":%u,\"bits_bad\":%u,",
+         a.first_bad_index, a.cus_seen, a.xcds_seen, a.simds_seen, a.cus_bad, a.xcd, a.se, a.sh,
+         a.cu, a.simd, a.first_fail_mask, a.n_bad, a.first_bad, a.bits_bad);
+  printf("\"first_bad_round\":%d,\"first_bad_record\":%d,\"grid_blocks\":%d,\"iters\":%d,"
+         "\"gpu_ms\":%.3f,\"t_total_ms\":%.3f,\"failed_test\":\"%s\",\"msg\":\"%s\"}",
+         r.first_bad_round, r.first_bad_record, r.grid_blocks, r.iters, r.gpu_ms, r.t_total_ms,
+         r.failed_test, r.msg);
+}
+
+int scrub_unavailable(const std::string& msg);
+void* load_entry(const char* soname, const char* symbol, std::string* why);
+
 // The quick probe first, then with --compute the compute-coverage stage, then
-// with --deep the data-integrity stage; a device that failed a stage is not
-// stressed further.  Top-level "ok" and "msg" cover all stages run.
+// with --formats the matrix-format stage, then with --deep the data-integrity
+// stage; a device that failed a stage is not stressed further.  Top-level "ok"
+// and "msg" cover all stages run.  The formats library is looked up before
+// anything runs: a probe that was asked for the stage and cannot run it says
+// so, in the scrubs' shape, and probes nothing.
 int cmd_probe_staged(int device, bool compute, const CroComputeOpts& copts, bool deep,
-                     const CroIntegrityOpts& opts) {
+                     const CroIntegrityOpts& opts, const CroFormatsOpts* fopts = nullptr) {
+  typedef int (*FormatsRun)(int, const CroFormatsOpts*, CroFormatsResult*);
+  FormatsRun run_formats = nullptr;
+  if (fopts) {
+    std::string why;
+    run_formats = (FormatsRun)load_entry("libcroformats.so", "cro_formats_run", &why);
+    if (run_formats == nullptr) return scrub_unavailable(why);
+  }
   CroProbeResult result;
   int rc = cro_probe_run(device, &result);
   CroComputeResult comp;
+  CroFormatsResult fmts;
   CroIntegrityResult integ;
-  bool ran_comp = false, ran = false;
+  bool ran_comp = false, ran_fmts = false, ran = false;
   bool ok = result.ok;
   const char* msg = result.msg;
   if (ok && compute) {
@@ -349,6 +385,14 @@ int cmd_probe_staged(int device, bool compute, const CroComputeOpts& copts, bool
     if (!comp.ok) {
       ok = false;
       msg = comp.msg;
+    }
+  }
+  if (ok && run_formats) {
+    run_formats(device, fopts, &fmts);
+    ran_fmts = true;
+    if (!fmts.ok) {
+      ok = false;
+      msg = fmts.msg;
     }
   }
   if (ok && deep) {
@@ -368,6 +412,10 @@ int cmd_probe_staged(int device, bool compute, const CroComputeOpts& copts, bool
   if (ran_comp) {
     printf(",");
     print_compute(comp);
+  }
+  if (ran_fmts) {
+    printf(",");
+    print_formats(fmts);
   }
   if (ran) {
     printf(",");
@@ -549,6 +597,9 @@ int main(int argc, char** argv) {
   bool regs = false;
   CroRegScrubOpts reg_opts;  // nor here
   memset(&reg_opts, 0, sizeof(reg_opts));
+  bool formats = false;
+  CroFormatsOpts formats_opts;  // nor here
+  memset(&formats_opts, 0, sizeof(formats_opts));
   for (int i = 2; i < argc; ++i) {
     std::string arg = argv[i];
     if (arg == "--sysroot" && i + 1 < argc) g_sysroot = argv[++i];
@@ -558,6 +609,8 @@ int main(int argc, char** argv) {
     else if (arg == "--deep") deep = true;
     else if (arg == "--compute") compute = true;
     else if (arg == "--compute-min-cu-fraction" && i + 1 < argc) compute_opts.min_cu_fraction = atof(argv[++i]);
+    else if (arg == "--formats") formats = true;
+    else if (arg == "--formats-min-cu-fraction" && i + 1 < argc) formats_opts.min_cu_fraction = atof(argv[++i]);
     else if (arg == "--vram-mib" && i + 1 < argc) integ_opts.vram_bytes = atoll(argv[++i]) << 20;
     else if (arg == "--link-mib" && i + 1 < argc) integ_opts.link_bytes = atoll(argv[++i]) << 20;
     else if (arg == "--link-floor-gbps" && i + 1 < argc) integ_opts.link_floor_gbps = atof(argv[++i]);
@@ -582,7 +635,8 @@ int main(int argc, char** argv) {
         return 1;
       }
     }
-    return cmd_probe_staged(device, compute, compute_opts, deep, integ_opts);
+    return cmd_probe_staged(device, compute, compute_opts, deep, integ_opts,
+                            formats ? &formats_opts : nullptr);
   }
   if (cmd == "scrub") {
     if (!bdf.empty()) {

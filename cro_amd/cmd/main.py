@@ -76,12 +76,27 @@ def add_probe_arguments(p: argparse.ArgumentParser) -> None:
                    help="compute probe: fail when fewer than this fraction of "
                    "the device's CUs were reached (0 = off: coverage is "
                    "reported, only data gates)")
+    p.add_argument("--probe-formats", choices=["off", "on"],
+                   default=env("CRO_PROBE_FORMATS", "off"),
+                   help="on: additionally run exact f16, fp8, bf8, block-scaled "
+                   "fp8/fp6/fp4 and f64 matrix checks on every CU and SIMD, at "
+                   "either level; a failure names the check, XCD, CU and SIMD")
+    p.add_argument("--probe-formats-min-cu-fraction", type=float,
+                   default=float(env("CRO_PROBE_FORMATS_MIN_CU_FRACTION", "0")),
+                   help="formats probe: fail when fewer than this fraction of "
+                   "the device's CUs were reached (0 = off: coverage is "
+                   "reported, only data gates)")
 
 
 def select_probe_fn(args):
     """The AmdNodeOps probe hook for the parsed --probe-* options."""
     from ..nodeops.probe import make_probe_fn
 
+    # a stage that is off passes no keyword of its own
+    stages = {}
+    if getattr(args, "probe_formats", "off") == "on":
+        stages.update(formats=True,
+                      formats_min_cu_fraction=args.probe_formats_min_cu_fraction)
     return make_probe_fn(
         args.probe_level,
         vram_bytes=args.probe_vram_mib << 20,
@@ -89,7 +104,29 @@ def select_probe_fn(args):
         link_floor_gbps=args.probe_link_floor_gbps,
         compute=args.probe_compute == "on",
         compute_min_cu_fraction=args.probe_compute_min_cu_fraction,
+        **stages,
     )
+
+
+def drop_unavailable_probe_stages(args, log) -> bool:
+    """The optional probe stage with a library of its own (--probe-formats)
+    that is on but whose library is not on this node: warn, switch the stage
+    off in ``args`` and go on without it.  True when it was switched off."""
+    if getattr(args, "probe_formats", "off") != "on":
+        return False
+    lib = None
+    try:
+        from ..nodeops.formats import load_formats_library
+
+        lib = load_formats_library(required=False)
+    except Exception:
+        pass
+    if lib is not None:
+        log.info("health probe matrix-format stage: on")
+        return False
+    log.warning("gfx950 matrix-format probe library unavailable; formats stage disabled")
+    args.probe_formats = "off"
+    return True
 
 
 def add_scrub_arguments(p: argparse.ArgumentParser) -> None:
@@ -421,6 +458,7 @@ def main(argv=None) -> int:
         from ..nodeops.probe import load_library
 
         if load_library(required=False) is not None:
+            drop_unavailable_probe_stages(args, log)
             probe_fn = select_probe_fn(args)
             if args.probe_level != "quick":
                 log.info("health probe level: %s", args.probe_level)

@@ -480,6 +480,20 @@ class ComposableResourceReconciler(Reconciler):
                     f"bits_bad=0x{int(compute.get('bits_bad', 0)):08x} "
                     f"cus_bad={compute.get('cus_bad')}: {probe}"
                 )
+            formats = probe.get("formats")
+            if isinstance(formats, dict) and not formats.get("ok", True):
+                # matrix-format stage: the same lead as the compute stage's
+                test = formats.get("failed_test") or (
+                    "coverage" if formats.get("rc") == -33 else "unknown"
+                )
+                self.metrics.probe_formats_failures_total.labels(test=test).inc()
+                raise FabricError(
+                    "gfx950 health probe failed: formats stage "
+                    f"{test} xcd={formats.get('xcd')} se={formats.get('se')} "
+                    f"cu={formats.get('cu')} simd={formats.get('simd')} "
+                    f"bits_bad=0x{int(formats.get('bits_bad', 0)):08x} "
+                    f"cus_bad={formats.get('cus_bad')}: {probe}"
+                )
             integrity = probe.get("integrity")
             if isinstance(integrity, dict) and not integrity.get("ok", True):
                 # deep level: lead with what an operator needs to act on —
@@ -509,6 +523,13 @@ class ComposableResourceReconciler(Reconciler):
                     f"; compute: {compute.get('cus_seen', 0)}/{compute.get('cus_expected', 0)}"
                     f" CUs, {compute.get('simds_seen', 0)} SIMDs,"
                     f" {compute.get('gpu_ms', 0):.1f} ms"
+                )
+            formats = probe.get("formats")
+            if isinstance(formats, dict):
+                probe_note += (
+                    f"; formats: {formats.get('cus_seen', 0)}/{formats.get('cus_expected', 0)}"
+                    f" CUs, {formats.get('simds_seen', 0)} SIMDs,"
+                    f" {formats.get('gpu_ms', 0):.1f} ms"
                 )
             integrity = probe.get("integrity")
             if isinstance(integrity, dict):

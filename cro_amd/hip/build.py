@@ -61,6 +61,17 @@ REG_SCRUB_HEADERS = [
     COVERAGE_HEADER,  # for cro_cov_decode
 ]
 REG_SCRUB_OUT = os.path.join(HIP_DIR, "libcroregscrub.so")
+# matrix-format probe stage: a library of its own as well (the probe
+# library's lists above are pinned by its tests); cromfma.h for the f32
+# result maps
+FORMATS_SRC = os.path.join(HIP_DIR, "formats.hip")
+FORMATS_HEADERS = [
+    os.path.join(HIP_DIR, "croformats.h"),
+    os.path.join(HIP_DIR, "crohost.h"),
+    os.path.join(HIP_DIR, "cromfma.h"),
+    COVERAGE_HEADER,  # for cro_cov_cu_key, cro_cov_decode and the LCG
+]
+FORMATS_OUT = os.path.join(HIP_DIR, "libcroformats.so")
 AGENT_SRC = os.path.join(AGENT_DIR, "croagent.cpp")
 AGENT_OUT = os.path.join(AGENT_DIR, "croagent")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -117,11 +128,22 @@ def build_reg_scrub(force: bool = False) -> str:
     return REG_SCRUB_OUT
 
 
+def build_formats(force: bool = False) -> str:
+    """libcroformats.so: the matrix-format probe stage (formats.hip)."""
+    if force or _stale(FORMATS_OUT, [FORMATS_SRC] + FORMATS_HEADERS):
+        subprocess.run(
+            [HIPCC, *DEVICE_FLAGS, "-fPIC", "-shared", FORMATS_SRC, "-o", FORMATS_OUT],
+            check=True,
+        )
+    return FORMATS_OUT
+
+
 def build_agent(force: bool = False) -> str:
     """croagent: the native node-agent CLI (links libcroprobe; loads
-    libcroscrub.so, libcroldsscrub.so and libcroregscrub.so at run time, so
-    those libraries are no inputs here, and neither are croscrub.h,
-    croldsscrub.h and croregscrub.h, which the agent includes: the input list below is pinned by
+    libcroscrub.so, libcroldsscrub.so, libcroregscrub.so and libcroformats.so
+    at run time, so those libraries are no inputs here, and neither are
+    croscrub.h, croldsscrub.h, croregscrub.h and croformats.h, which the agent
+    includes: the input list below is pinned by
     tests/test_probe_compute.py.  A --force build, which is what `make build`
     does, picks up a change of those headers)."""
     if not force and not _stale(AGENT_OUT, [AGENT_SRC, HEADERS[0], COVERAGE_HEADER, OUT]):
@@ -150,4 +172,5 @@ if __name__ == "__main__":
     print(AGENT_OUT)
     print(build_scrub(force="--force" in sys.argv))
     print(build_lds_scrub(force="--force" in sys.argv))
+    print(build_formats(force="--force" in sys.argv))
     print(build_reg_scrub(force="--force" in sys.argv))

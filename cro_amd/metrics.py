@@ -81,6 +81,13 @@ class Metrics:
             "for the optional CU-coverage floor)",
             ["test"],
         )
+        self.probe_formats_failures_total = Counter(
+            "cro_probe_formats_failures_total",
+            "Attaches refused by the probe's matrix-format stage, by the check "
+            "that failed (mfma_f16, mfma_fp8, mfma_bf8, mx_fp8, mx_fp6, mx_fp4, "
+            "mfma_f64; coverage for the optional CU-coverage floor)",
+            ["test"],
+        )
         self.scrub_failures_total = Counter(
             "cro_scrub_failures_total",
             "Scrubs before drain that did not pass, by reason (residue: words "
@@ -114,6 +121,7 @@ class Metrics:
                 cls._singleton.devices_online,
                 cls._singleton.probe_integrity_failures_total,
                 cls._singleton.probe_compute_failures_total,
+                cls._singleton.probe_formats_failures_total,
                 cls._singleton.scrub_failures_total,
                 cls._singleton.scrub_seconds,
                 cls._singleton.scrub_bytes_total,

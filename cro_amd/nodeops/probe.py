@@ -895,7 +895,8 @@ def aggregate_records(records) -> dict:
 
 def make_probe_fn(level: str = "quick", vram_bytes: int = 0, link_bytes: int = 0,
                   link_floor_gbps: float = 0.0, seed: int = 0, compute: bool = False,
-                  compute_min_cu_fraction: float = 0.0):
+                  compute_min_cu_fraction: float = 0.0, formats: bool = False,
+                  formats_min_cu_fraction: float = 0.0):
     """AmdNodeOps probe hook for a probe level.
 
     ``quick`` is the rate/matrix-pipe gate.  ``deep`` runs it first and, only
@@ -907,10 +908,14 @@ def make_probe_fn(level: str = "quick", vram_bytes: int = 0, link_bytes: int = 0
     the two: quick, then compute, then (``deep``) integrity, stopping at the
     first stage that fails.  Its result nests under ``"compute"``; ``ok`` is
     the AND of the stages run and ``msg`` the failing stage's.
+
+    ``formats=True`` adds the matrix-format stage (nodeops/formats.py) after
+    the compute stage and before integrity, in the same way; its result nests
+    under ``"formats"``.
     """
     if level not in PROBE_LEVELS:
         raise ValueError(f"unknown probe level {level!r} (expected one of {PROBE_LEVELS})")
-    if level == "quick" and not compute:
+    if level == "quick" and not compute and not formats:
         return probe_fn_for_nodeops
 
     def staged_probe(gpu) -> dict:
@@ -927,6 +932,15 @@ def make_probe_fn(level: str = "quick", vram_bytes: int = 0, link_bytes: int = 0
                 result["ok"] = False
                 result["msg"] = stage.get("msg", "compute probe failed")
                 return result
+        if formats:
+            from .formats import run_formats
+
+            stage = run_formats(dev, seed=seed, min_cu_fraction=formats_min_cu_fraction)
+            result["formats"] = stage
+            if not stage.get("ok"):
+                result["ok"] = False
+                result["msg"] = stage.get("msg", "formats probe failed")
+                return result
         if level == "deep":
             integrity = run_integrity(
                 dev, vram_bytes=vram_bytes, link_bytes=link_bytes, seed=seed,
@@ -940,6 +954,8 @@ def make_probe_fn(level: str = "quick", vram_bytes: int = 0, link_bytes: int = 0
 
     staged_probe.level = level
     staged_probe.compute = bool(compute)
+    if formats:
+        staged_probe.formats = True
     return staged_probe
 
 
@@ -949,6 +965,15 @@ def _compute_argv(compute, compute_min_cu_fraction) -> list:
     argv = ["--compute"]
     if compute_min_cu_fraction:
         argv += ["--compute-min-cu-fraction", str(float(compute_min_cu_fraction))]
+    return argv
+
+
+def _formats_argv(formats, formats_min_cu_fraction) -> list:
+    if not formats:
+        return []
+    argv = ["--formats"]
+    if formats_min_cu_fraction:
+        argv += ["--formats-min-cu-fraction", str(float(formats_min_cu_fraction))]
     return argv
 
 
@@ -969,13 +994,15 @@ def _deep_argv(level: str, vram_mib, link_mib, link_floor_gbps) -> list:
 
 def probe_via_exec(execer, node: str, gpu, argv_prefix=None, level: str = "quick",
                    vram_mib=None, link_mib=None, link_floor_gbps=0, compute: bool = False,
-                   compute_min_cu_fraction=0) -> dict:
+                   compute_min_cu_fraction=0, formats: bool = False,
+                   formats_min_cu_fraction=0) -> dict:
     """Health probe through the node agent (``croagent probe --bdf``) — the
     cluster shape where controllers run off-node and reach hardware only
     through the NodeExec seam.  Returns the same dict shape as run_probe
     (at level ``deep``: as make_probe_fn("deep"), via ``croagent probe
     --deep`` and the size options given; with ``compute``: as
-    make_probe_fn(..., compute=True), via ``--compute``).
+    make_probe_fn(..., compute=True), via ``--compute``; with ``formats``:
+    via ``--formats``).
 
     ``argv_prefix`` wraps the command for the container-driver arm (e.g.
     ``["chroot", "/run/amdgpu-driver"]`` so the probe runs against the
@@ -987,6 +1014,7 @@ def probe_via_exec(execer, node: str, gpu, argv_prefix=None, level: str = "quick
     argv = list(argv_prefix or []) + ["croagent", "probe", "--bdf", gpu.pci_bdf]
     argv += _deep_argv(level, vram_mib, link_mib, link_floor_gbps)
     argv += _compute_argv(compute, compute_min_cu_fraction)
+    argv += _formats_argv(formats, formats_min_cu_fraction)
     rc, out, err = execer.run(node, argv, timeout=300)
     if rc != 0 and not out.strip():
         return {"ok": False, "rc": rc, "msg": err.strip() or "croagent probe failed"}
@@ -998,7 +1026,8 @@ def probe_via_exec(execer, node: str, gpu, argv_prefix=None, level: str = "quick
 
 def make_exec_probe_fn(execer, node: str, argv_prefix_fn=None, level: str = "quick",
                        vram_mib=None, link_mib=None, link_floor_gbps=0, compute: bool = False,
-                       compute_min_cu_fraction=0):
+                       compute_min_cu_fraction=0, formats: bool = False,
+                       formats_min_cu_fraction=0):
     """AmdNodeOps probe hook bound to a NodeExec (local or remote agent).
 
     ``argv_prefix_fn()`` is resolved per probe so a driver-mode change
@@ -1007,12 +1036,17 @@ def make_exec_probe_fn(execer, node: str, argv_prefix_fn=None, level: str = "qui
     """
     _deep_argv(level, vram_mib, link_mib, link_floor_gbps)  # reject a bad level now
 
+    # a stage that is off passes no keyword of its own
+    stages = {}
+    if formats:
+        stages.update(formats=True, formats_min_cu_fraction=formats_min_cu_fraction)
+
     def probe(gpu):
         prefix = argv_prefix_fn() if argv_prefix_fn else None
         return probe_via_exec(
             execer, node, gpu, argv_prefix=prefix, level=level, vram_mib=vram_mib,
             link_mib=link_mib, link_floor_gbps=link_floor_gbps, compute=compute,
-            compute_min_cu_fraction=compute_min_cu_fraction,
+            compute_min_cu_fraction=compute_min_cu_fraction, **stages,
         )
 
     return probe
