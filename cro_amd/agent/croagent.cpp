@@ -16,6 +16,9 @@
 //       [--compute [--compute-min-cu-fraction X]]
 //       [--formats [--formats-min-cu-fraction X]]  + the matrix-format stage
 //                                            (libcroformats.so, loaded at run time)
+//       [--coherence [--coherence-min-cu-fraction X]]  + the coherence stage:
+//                                            atomic units and cross-CU visibility
+//                                            (libcrocoherence.so, loaded at run time)
 //                                            + exact checks on every CU and SIMD
 //   croagent scrub  [--device N | --bdf B]   overwrite and verify VRAM before drain
 //       [--max-mib N] [--reserve-mib N] [--min-fraction X]
@@ -38,6 +41,7 @@
 #include "../hip/croprobe.h"
 #include "../hip/croldsscrub.h"
 #include "../hip/croformats.h"
+#include "../hip/crocoherence.h"
 #include "../hip/croregscrub.h"
 #include "../hip/croscrub.h"
 
@@ -353,17 +357,43 @@ void print_formats(const CroFormatsResult& r) {
          r.failed_test, r.msg);
 }
 
+// The coherence stage's result, keys as nodeops/coherence.py run_coherence.
+void print_coherence(const CroCoherenceResult& r) {
+  const CroCoherenceAgg& a = r.agg;
+  printf("\"coherence\":{\"ok\":%s,\"rc\":%d,\"cus_expected\":%d,\"rounds\":%d,"
+         "\"waves_run\":%llu,\"waves_bad\":%llu,",
+         r.ok ? "true" : "false", r.rc, r.cus_expected, r.rounds, a.waves_run, a.waves_bad);
+  for (int t = 0; t < CRO_COH_TESTS; ++t) printf("\"bad_%s\":%llu,", kCroCohTestNames[t], a.bad[t]);
+  printf("\"pairs_checked\":%llu,\"pairs_expected\":%llu,\"vis_bad\":%llu,\"vis_stale\":%llu,"
+         "\"tally_got\":%llu,\"tally_want\":%llu,\"first_bad_index\":%lld,\"cus_seen\":%d,"
+         "\"xcds_seen\":%d,\"simds_seen\":%d,\"cus_bad\":%d,\"xcd\":%d,\"se\":%d,\"sh\":%d,"
+         "\"cu\":%d,\"simd\":%d,\"fail_mask\":%u,\"first_fail_mask\":%u,\"n_bad\":%u,"
+         "\"first_bad\":%u,\"bits_bad\":%u,\"tally_level\":%d,\"tally_slot\":%d,"
+         "\"tally_unit\":%d,\"tally_epoch\":%d,\"bad_block\":%d,\"ticket_slot\":%d,"
+         "\"ticket_epoch\":%d,\"ticket_seen\":%u,\"ticket_owner\":%u,",
+         a.pairs_checked, a.pairs_expected, a.vis_bad, a.vis_stale, a.tally_got, a.tally_want,
+         a.first_bad_index, a.cus_seen, a.xcds_seen, a.simds_seen, a.cus_bad, a.xcd, a.se, a.sh,
+         a.cu, a.simd, a.fail_mask, a.first_fail_mask, a.n_bad, a.first_bad, a.bits_bad,
+         a.tally_level, a.tally_slot, a.tally_unit, a.tally_epoch, a.bad_block, a.ticket_slot,
+         a.ticket_epoch, a.ticket_seen, a.ticket_owner);
+  printf("\"first_bad_round\":%d,\"first_bad_record\":%d,\"grid_blocks\":%d,\"iters\":%d,"
+         "\"gpu_ms\":%.3f,\"t_total_ms\":%.3f,\"failed_test\":\"%s\",\"msg\":\"%s\"}",
+         r.first_bad_round, r.first_bad_record, r.grid_blocks, r.iters, r.gpu_ms, r.t_total_ms,
+         r.failed_test, r.msg);
+}
+
 int scrub_unavailable(const std::string& msg);
 void* load_entry(const char* soname, const char* symbol, std::string* why);
 
 // The quick probe first, then with --compute the compute-coverage stage, then
-// with --formats the matrix-format stage, then with --deep the data-integrity
-// stage; a device that failed a stage is not stressed further.  Top-level "ok"
-// and "msg" cover all stages run.  The formats library is looked up before
-// anything runs: a probe that was asked for the stage and cannot run it says
+// with --formats the matrix-format stage, then with --coherence the coherence
+// stage, then with --deep the data-integrity stage; a device that failed a
+// stage is not stressed further.  Top-level "ok" and "msg" cover all stages
+// run.  The formats and coherence libraries are looked up before anything runs: a probe that was asked for the stage and cannot run it says
 // so, in the scrubs' shape, and probes nothing.
 int cmd_probe_staged(int device, bool compute, const CroComputeOpts& copts, bool deep,
-                     const CroIntegrityOpts& opts, const CroFormatsOpts* fopts = nullptr) {
+                     const CroIntegrityOpts& opts, const CroFormatsOpts* fopts = nullptr,
+                     const CroCoherenceOpts* hopts = nullptr) {
   typedef int (*FormatsRun)(int, const CroFormatsOpts*, CroFormatsResult*);
   FormatsRun run_formats = nullptr;
   if (fopts) {
@@ -371,12 +401,20 @@ int cmd_probe_staged(int device, bool compute, const CroComputeOpts& copts, bool
     run_formats = (FormatsRun)load_entry("libcroformats.so", "cro_formats_run", &why);
     if (run_formats == nullptr) return scrub_unavailable(why);
   }
+  typedef int (*CoherenceRun)(int, const CroCoherenceOpts*, CroCoherenceResult*);
+  CoherenceRun run_coherence = nullptr;
+  if (hopts) {
+    std::string why;
+    run_coherence = (CoherenceRun)load_entry("libcrocoherence.so", "cro_coherence_run", &why);
+    if (run_coherence == nullptr) return scrub_unavailable(why);
+  }
   CroProbeResult result;
   int rc = cro_probe_run(device, &result);
   CroComputeResult comp;
   CroFormatsResult fmts;
+  CroCoherenceResult coh;
   CroIntegrityResult integ;
-  bool ran_comp = false, ran_fmts = false, ran = false;
+  bool ran_comp = false, ran_fmts = false, ran_coh = false, ran = false;
   bool ok = result.ok;
   const char* msg = result.msg;
   if (ok && compute) {
@@ -393,6 +431,14 @@ int cmd_probe_staged(int device, bool compute, const CroComputeOpts& copts, bool
     if (!fmts.ok) {
       ok = false;
       msg = fmts.msg;
+    }
+  }
+  if (ok && run_coherence) {
+    run_coherence(device, hopts, &coh);
+    ran_coh = true;
+    if (!coh.ok) {
+      ok = false;
+      msg = coh.msg;
     }
   }
   if (ok && deep) {
@@ -416,6 +462,10 @@ int cmd_probe_staged(int device, bool compute, const CroComputeOpts& copts, bool
   if (ran_fmts) {
     printf(",");
     print_formats(fmts);
+  }
+  if (ran_coh) {
+    printf(",");
+    print_coherence(coh);
   }
   if (ran) {
     printf(",");
@@ -600,6 +650,9 @@ int main(int argc, char** argv) {
   bool formats = false;
   CroFormatsOpts formats_opts;  // nor here
   memset(&formats_opts, 0, sizeof(formats_opts));
+  bool coherence = false;
+  CroCoherenceOpts coherence_opts;  // nor here
+  memset(&coherence_opts, 0, sizeof(coherence_opts));
   for (int i = 2; i < argc; ++i) {
     std::string arg = argv[i];
     if (arg == "--sysroot" && i + 1 < argc) g_sysroot = argv[++i];
@@ -611,6 +664,8 @@ int main(int argc, char** argv) {
     else if (arg == "--compute-min-cu-fraction" && i + 1 < argc) compute_opts.min_cu_fraction = atof(argv[++i]);
     else if (arg == "--formats") formats = true;
     else if (arg == "--formats-min-cu-fraction" && i + 1 < argc) formats_opts.min_cu_fraction = atof(argv[++i]);
+    else if (arg == "--coherence") coherence = true;
+    else if (arg == "--coherence-min-cu-fraction" && i + 1 < argc) coherence_opts.min_cu_fraction = atof(argv[++i]);
     else if (arg == "--vram-mib" && i + 1 < argc) integ_opts.vram_bytes = atoll(argv[++i]) << 20;
     else if (arg == "--link-mib" && i + 1 < argc) integ_opts.link_bytes = atoll(argv[++i]) << 20;
     else if (arg == "--link-floor-gbps" && i + 1 < argc) integ_opts.link_floor_gbps = atof(argv[++i]);
@@ -636,7 +691,8 @@ int main(int argc, char** argv) {
       }
     }
     return cmd_probe_staged(device, compute, compute_opts, deep, integ_opts,
-                            formats ? &formats_opts : nullptr);
+                            formats ? &formats_opts : nullptr,
+                            coherence ? &coherence_opts : nullptr);
   }
   if (cmd == "scrub") {
     if (!bdf.empty()) {

@@ -86,6 +86,17 @@ def add_probe_arguments(p: argparse.ArgumentParser) -> None:
                    help="formats probe: fail when fewer than this fraction of "
                    "the device's CUs were reached (0 = off: coverage is "
                    "reported, only data gates)")
+    p.add_argument("--probe-coherence", choices=["off", "on"],
+                   default=env("CRO_PROBE_COHERENCE", "off"),
+                   help="on: additionally run exact checks of the atomic units (L2 / "
+                   "memory and LDS) and of cross-CU, cross-XCD visibility on every CU, "
+                   "at either level; a failure names the check and the XCD, CU and "
+                   "SIMD, or the tally line")
+    p.add_argument("--probe-coherence-min-cu-fraction", type=float,
+                   default=float(env("CRO_PROBE_COHERENCE_MIN_CU_FRACTION", "0")),
+                   help="coherence probe: fail when fewer than this fraction of "
+                   "the device's CUs were reached (0 = off: coverage is "
+                   "reported, only data gates)")
 
 
 def select_probe_fn(args):
@@ -97,6 +108,9 @@ def select_probe_fn(args):
     if getattr(args, "probe_formats", "off") == "on":
         stages.update(formats=True,
                       formats_min_cu_fraction=args.probe_formats_min_cu_fraction)
+    if getattr(args, "probe_coherence", "off") == "on":
+        stages.update(coherence=True,
+                      coherence_min_cu_fraction=args.probe_coherence_min_cu_fraction)
     return make_probe_fn(
         args.probe_level,
         vram_bytes=args.probe_vram_mib << 20,
@@ -109,24 +123,40 @@ def select_probe_fn(args):
 
 
 def drop_unavailable_probe_stages(args, log) -> bool:
-    """The optional probe stage with a library of its own (--probe-formats)
-    that is on but whose library is not on this node: warn, switch the stage
-    off in ``args`` and go on without it.  True when it was switched off."""
-    if getattr(args, "probe_formats", "off") != "on":
-        return False
-    lib = None
-    try:
-        from ..nodeops.formats import load_formats_library
+    """An optional probe stage with a library of its own (--probe-formats,
+    --probe-coherence) that is on but whose library is not on this node: warn,
+    switch the stage off in ``args`` and go on without it.  True when one was
+    switched off."""
+    dropped = False
+    if getattr(args, "probe_formats", "off") == "on":
+        lib = None
+        try:
+            from ..nodeops.formats import load_formats_library
 
-        lib = load_formats_library(required=False)
-    except Exception:
-        pass
-    if lib is not None:
-        log.info("health probe matrix-format stage: on")
-        return False
-    log.warning("gfx950 matrix-format probe library unavailable; formats stage disabled")
-    args.probe_formats = "off"
-    return True
+            lib = load_formats_library(required=False)
+        except Exception:
+            pass
+        if lib is not None:
+            log.info("health probe matrix-format stage: on")
+        else:
+            log.warning("gfx950 matrix-format probe library unavailable; formats stage disabled")
+            args.probe_formats = "off"
+            dropped = True
+    if getattr(args, "probe_coherence", "off") == "on":
+        lib = None
+        try:
+            from ..nodeops.coherence import load_coherence_library
+
+            lib = load_coherence_library(required=False)
+        except Exception:
+            pass
+        if lib is not None:
+            log.info("health probe coherence stage: on")
+        else:
+            log.warning("gfx950 coherence probe library unavailable; coherence stage disabled")
+            args.probe_coherence = "off"
+            dropped = True
+    return dropped
 
 
 def add_scrub_arguments(p: argparse.ArgumentParser) -> None:

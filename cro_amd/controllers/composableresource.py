@@ -494,6 +494,30 @@ class ComposableResourceReconciler(Reconciler):
                     f"bits_bad=0x{int(formats.get('bits_bad', 0)):08x} "
                     f"cus_bad={formats.get('cus_bad')}: {probe}"
                 )
+            coherence = probe.get("coherence")
+            if isinstance(coherence, dict) and not coherence.get("ok", True):
+                # coherence stage: the check, then where: the place of a wave
+                # or a workgroup line, or the tally line and slot
+                test = coherence.get("failed_test") or (
+                    "coverage" if coherence.get("rc") == -35 else "unknown"
+                )
+                self.metrics.probe_coherence_failures_total.labels(test=test).inc()
+                where = (
+                    f"xcd={coherence.get('xcd')} se={coherence.get('se')} "
+                    f"cu={coherence.get('cu')} simd={coherence.get('simd')}"
+                )
+                level = coherence.get("tally_level", -1)
+                if isinstance(level, int) and 0 <= level <= 2:
+                    where += (
+                        f" level={('workgroup', 'xcd', 'device')[level]}"
+                        f" line={coherence.get('tally_unit')} slot={coherence.get('tally_slot')}"
+                        f" got=0x{int(coherence.get('tally_got', 0)):x}"
+                        f" want=0x{int(coherence.get('tally_want', 0)):x}"
+                    )
+                raise FabricError(
+                    f"gfx950 health probe failed: coherence stage {test} {where} "
+                    f"block={coherence.get('bad_block')} cus_bad={coherence.get('cus_bad')}: {probe}"
+                )
             integrity = probe.get("integrity")
             if isinstance(integrity, dict) and not integrity.get("ok", True):
                 # deep level: lead with what an operator needs to act on —
@@ -530,6 +554,14 @@ class ComposableResourceReconciler(Reconciler):
                     f"; formats: {formats.get('cus_seen', 0)}/{formats.get('cus_expected', 0)}"
                     f" CUs, {formats.get('simds_seen', 0)} SIMDs,"
                     f" {formats.get('gpu_ms', 0):.1f} ms"
+                )
+            coherence = probe.get("coherence")
+            if isinstance(coherence, dict):
+                probe_note += (
+                    f"; coherence: {coherence.get('cus_seen', 0)}"
+                    f"/{coherence.get('cus_expected', 0)} CUs,"
+                    f" {coherence.get('pairs_checked', 0)} pairs,"
+                    f" {coherence.get('gpu_ms', 0):.1f} ms"
                 )
             integrity = probe.get("integrity")
             if isinstance(integrity, dict):

@@ -72,6 +72,15 @@ FORMATS_HEADERS = [
     COVERAGE_HEADER,  # for cro_cov_cu_key, cro_cov_decode and the LCG
 ]
 FORMATS_OUT = os.path.join(HIP_DIR, "libcroformats.so")
+# coherence probe stage (atomics and cross-CU visibility): a library of its
+# own too (the lists above are pinned by their tests)
+COHERENCE_SRC = os.path.join(HIP_DIR, "coherence.hip")
+COHERENCE_HEADERS = [
+    os.path.join(HIP_DIR, "crocoherence.h"),
+    os.path.join(HIP_DIR, "crohost.h"),
+    COVERAGE_HEADER,  # for cro_cov_cu_key and cro_cov_decode
+]
+COHERENCE_OUT = os.path.join(HIP_DIR, "libcrocoherence.so")
 AGENT_SRC = os.path.join(AGENT_DIR, "croagent.cpp")
 AGENT_OUT = os.path.join(AGENT_DIR, "croagent")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -138,11 +147,22 @@ def build_formats(force: bool = False) -> str:
     return FORMATS_OUT
 
 
+def build_coherence(force: bool = False) -> str:
+    """libcrocoherence.so: the coherence probe stage (coherence.hip)."""
+    if force or _stale(COHERENCE_OUT, [COHERENCE_SRC] + COHERENCE_HEADERS):
+        subprocess.run(
+            [HIPCC, *DEVICE_FLAGS, "-fPIC", "-shared", COHERENCE_SRC, "-o", COHERENCE_OUT],
+            check=True,
+        )
+    return COHERENCE_OUT
+
+
 def build_agent(force: bool = False) -> str:
     """croagent: the native node-agent CLI (links libcroprobe; loads
-    libcroscrub.so, libcroldsscrub.so, libcroregscrub.so and libcroformats.so
-    at run time, so those libraries are no inputs here, and neither are
-    croscrub.h, croldsscrub.h, croregscrub.h and croformats.h, which the agent
+    libcroscrub.so, libcroldsscrub.so, libcroregscrub.so, libcroformats.so and
+    libcrocoherence.so at run time, so those libraries are no inputs here, and
+    neither are croscrub.h, croldsscrub.h, croregscrub.h, croformats.h and
+    crocoherence.h, which the agent
     includes: the input list below is pinned by
     tests/test_probe_compute.py.  A --force build, which is what `make build`
     does, picks up a change of those headers)."""
@@ -173,4 +193,5 @@ if __name__ == "__main__":
     print(build_scrub(force="--force" in sys.argv))
     print(build_lds_scrub(force="--force" in sys.argv))
     print(build_formats(force="--force" in sys.argv))
+    print(build_coherence(force="--force" in sys.argv))
     print(build_reg_scrub(force="--force" in sys.argv))

@@ -88,6 +88,14 @@ class Metrics:
             "mfma_f64; coverage for the optional CU-coverage floor)",
             ["test"],
         )
+        self.probe_coherence_failures_total = Counter(
+            "cro_probe_coherence_failures_total",
+            "Attaches refused by the probe's coherence stage, by the check that "
+            "failed (add_u32, add_u64, add_f32, add_f64, pk_add_f16, pk_add_bf16, "
+            "minmax, bitwise, ticket, cas, lds_rmw, visibility; coverage for the "
+            "optional CU-coverage floor)",
+            ["test"],
+        )
         self.scrub_failures_total = Counter(
             "cro_scrub_failures_total",
             "Scrubs before drain that did not pass, by reason (residue: words "
@@ -122,6 +130,7 @@ class Metrics:
                 cls._singleton.probe_integrity_failures_total,
                 cls._singleton.probe_compute_failures_total,
                 cls._singleton.probe_formats_failures_total,
+                cls._singleton.probe_coherence_failures_total,
                 cls._singleton.scrub_failures_total,
                 cls._singleton.scrub_seconds,
                 cls._singleton.scrub_bytes_total,

@@ -896,7 +896,8 @@ def aggregate_records(records) -> dict:
 def make_probe_fn(level: str = "quick", vram_bytes: int = 0, link_bytes: int = 0,
                   link_floor_gbps: float = 0.0, seed: int = 0, compute: bool = False,
                   compute_min_cu_fraction: float = 0.0, formats: bool = False,
-                  formats_min_cu_fraction: float = 0.0):
+                  formats_min_cu_fraction: float = 0.0, coherence: bool = False,
+                  coherence_min_cu_fraction: float = 0.0):
     """AmdNodeOps probe hook for a probe level.
 
     ``quick`` is the rate/matrix-pipe gate.  ``deep`` runs it first and, only
@@ -912,10 +913,15 @@ def make_probe_fn(level: str = "quick", vram_bytes: int = 0, link_bytes: int = 0
     ``formats=True`` adds the matrix-format stage (nodeops/formats.py) after
     the compute stage and before integrity, in the same way; its result nests
     under ``"formats"``.
+
+    ``coherence=True`` adds the coherence stage (nodeops/coherence.py: the
+    atomic units and cross-CU visibility) after the formats stage and before
+    integrity, in the same way; its result nests under ``"coherence"``.  The
+    order is quick, compute, formats, coherence, integrity.
     """
     if level not in PROBE_LEVELS:
         raise ValueError(f"unknown probe level {level!r} (expected one of {PROBE_LEVELS})")
-    if level == "quick" and not compute and not formats:
+    if level == "quick" and not compute and not formats and not coherence:
         return probe_fn_for_nodeops
 
     def staged_probe(gpu) -> dict:
@@ -941,6 +947,15 @@ def make_probe_fn(level: str = "quick", vram_bytes: int = 0, link_bytes: int = 0
                 result["ok"] = False
                 result["msg"] = stage.get("msg", "formats probe failed")
                 return result
+        if coherence:
+            from .coherence import run_coherence
+
+            stage = run_coherence(dev, seed=seed, min_cu_fraction=coherence_min_cu_fraction)
+            result["coherence"] = stage
+            if not stage.get("ok"):
+                result["ok"] = False
+                result["msg"] = stage.get("msg", "coherence probe failed")
+                return result
         if level == "deep":
             integrity = run_integrity(
                 dev, vram_bytes=vram_bytes, link_bytes=link_bytes, seed=seed,
@@ -956,6 +971,8 @@ def make_probe_fn(level: str = "quick", vram_bytes: int = 0, link_bytes: int = 0
     staged_probe.compute = bool(compute)
     if formats:
         staged_probe.formats = True
+    if coherence:
+        staged_probe.coherence = True
     return staged_probe
 
 
@@ -977,6 +994,15 @@ def _formats_argv(formats, formats_min_cu_fraction) -> list:
     return argv
 
 
+def _coherence_argv(coherence, coherence_min_cu_fraction) -> list:
+    if not coherence:
+        return []
+    argv = ["--coherence"]
+    if coherence_min_cu_fraction:
+        argv += ["--coherence-min-cu-fraction", str(float(coherence_min_cu_fraction))]
+    return argv
+
+
 def _deep_argv(level: str, vram_mib, link_mib, link_floor_gbps) -> list:
     if level == "quick":
         return []
@@ -995,14 +1021,15 @@ def _deep_argv(level: str, vram_mib, link_mib, link_floor_gbps) -> list:
 def probe_via_exec(execer, node: str, gpu, argv_prefix=None, level: str = "quick",
                    vram_mib=None, link_mib=None, link_floor_gbps=0, compute: bool = False,
                    compute_min_cu_fraction=0, formats: bool = False,
-                   formats_min_cu_fraction=0) -> dict:
+                   formats_min_cu_fraction=0, coherence: bool = False,
+                   coherence_min_cu_fraction=0) -> dict:
     """Health probe through the node agent (``croagent probe --bdf``) — the
     cluster shape where controllers run off-node and reach hardware only
     through the NodeExec seam.  Returns the same dict shape as run_probe
     (at level ``deep``: as make_probe_fn("deep"), via ``croagent probe
     --deep`` and the size options given; with ``compute``: as
     make_probe_fn(..., compute=True), via ``--compute``; with ``formats``:
-    via ``--formats``).
+    via ``--formats``; with ``coherence``: via ``--coherence``).
 
     ``argv_prefix`` wraps the command for the container-driver arm (e.g.
     ``["chroot", "/run/amdgpu-driver"]`` so the probe runs against the
@@ -1015,6 +1042,7 @@ def probe_via_exec(execer, node: str, gpu, argv_prefix=None, level: str = "quick
     argv += _deep_argv(level, vram_mib, link_mib, link_floor_gbps)
     argv += _compute_argv(compute, compute_min_cu_fraction)
     argv += _formats_argv(formats, formats_min_cu_fraction)
+    argv += _coherence_argv(coherence, coherence_min_cu_fraction)
     rc, out, err = execer.run(node, argv, timeout=300)
     if rc != 0 and not out.strip():
         return {"ok": False, "rc": rc, "msg": err.strip() or "croagent probe failed"}
@@ -1027,7 +1055,8 @@ def probe_via_exec(execer, node: str, gpu, argv_prefix=None, level: str = "quick
 def make_exec_probe_fn(execer, node: str, argv_prefix_fn=None, level: str = "quick",
                        vram_mib=None, link_mib=None, link_floor_gbps=0, compute: bool = False,
                        compute_min_cu_fraction=0, formats: bool = False,
-                       formats_min_cu_fraction=0):
+                       formats_min_cu_fraction=0, coherence: bool = False,
+                       coherence_min_cu_fraction=0):
     """AmdNodeOps probe hook bound to a NodeExec (local or remote agent).
 
     ``argv_prefix_fn()`` is resolved per probe so a driver-mode change
@@ -1040,6 +1069,8 @@ def make_exec_probe_fn(execer, node: str, argv_prefix_fn=None, level: str = "qui
     stages = {}
     if formats:
         stages.update(formats=True, formats_min_cu_fraction=formats_min_cu_fraction)
+    if coherence:
+        stages.update(coherence=True, coherence_min_cu_fraction=coherence_min_cu_fraction)
 
     def probe(gpu):
         prefix = argv_prefix_fn() if argv_prefix_fn else None
