@@ -19,10 +19,10 @@ struct CroProbeResult {
   double bf16_tflops;  // dense bf16 MFMA issue rate
   long long vram_total;
   long long vram_free;
-  double t_setup_ms;  // host wall per probe section (attach-latency budget)
-  double t_mfma_ms;
-  double t_bw_ms;
-  double t_bf16_ms;
+  double t_setup_ms;  // host wall from the entry to the first enqueue
+  double t_mfma_ms;   // device time of each section, from the events around it:
+  double t_bw_ms;     // the probe is one submission with one wait, so there is
+  double t_bf16_ms;   // no host wall per section (attach-latency budget)
   char gcn_arch[64];
   char msg[256];
 };
@@ -45,6 +45,25 @@ struct CroProbeOpts {
 // mismatch, -3 HBM bandwidth below its floor, -4 bf16 rate below its floor.
 int cro_probe_run(int device, struct CroProbeResult* out);  // = run_opts(device, NULL, out)
 int cro_probe_run_opts(int device, const struct CroProbeOpts* opts, struct CroProbeResult* out);
+
+// Lengths of the probe's two rate windows; 0 takes the library default, which
+// is what cro_probe_run_opts runs at (profiles/quick_probe_windows_mi355x.md
+// has the sweep behind the defaults).  nodeops/probe.py mirrors the struct
+// (tests/test_probe_windows.py compares sizeof/offsetof).
+struct CroProbeWindows {
+  int copy_launches;  // launches of the 2 x 256 MiB copy; at most 64
+  int bf16_iters;     // iterations of the rate kernel; at most 65536
+  // Test seam: 1 leaves the check kernel out, so the exact gate sees the
+  // tile as the in-stream poison left it and must fail with rc -2.
+  int skip_check_launch;
+  int reserved;
+};
+
+// The probe's pipeline at these windows (NULL: the defaults), floors at their
+// defaults; rc as cro_probe_run_opts.  A negative field or one above its
+// limit is a bad argument.
+int cro_probe_run_windows(int device, const struct CroProbeWindows* w,
+                          struct CroProbeResult* out);
 // Raw entries for tests, one per kernel of the quick probe (probe.hip).
 // -10 = bad argument.  K a multiple of 4, at most 4096.
 int cro_probe_mfma_f32(int device, const float* A, const float* B, float* D, int K);

@@ -19,6 +19,20 @@
 //      independent accumulators per wave; reports matrix-core TFLOP/s
 //      (healthy ≈2.3-2.5 PF; loose floor gate).
 //
+// A call is one submission and one wait.  The check kernel's inputs and the
+// expected tile never change, so the context holds them (built and uploaded
+// once per device).  On the context's own non-blocking stream a call
+// enqueues: a poison of the result tile, the check kernel, the copy
+// launches, the rate kernel and the tile's copy into pinned host memory, with
+// an event between the sections; it then waits once, on the last event, and
+// compares the tile and takes both rates from event pairs.  t_mfma_ms,
+// t_bw_ms and t_bf16_ms are therefore each section's device time from its
+// events (with a single wait there is no host wall per section); t_setup_ms
+// is the host wall up to the first enqueue.  The lengths of the two rate
+// windows (copy launches, rate-kernel iterations) are the defaults below,
+// set against a sweep on the device (profiles/quick_probe_windows_mi355x.md);
+// cro_probe_run_windows runs the same pipeline at a caller's windows.
+//
 // Built with hipcc for gfx950 only (no torch dependency), with integrity.hip
 // and coverage.hip, into libcroprobe.so (cro_amd/hip/build.py).  The three
 // sources share their host plumbing (crohost.h) and, probe.hip and
@@ -101,15 +115,26 @@ __global__ void mfma_bf16_rate_kernel(float* __restrict__ out, int iters) {
 // host driver
 // ---------------------------------------------------------------------------
 
+// Events of one call, in stream order: around the check kernel, after the
+// copy launches, after the rate kernel, after the tile's copy to the host.
+enum { kEvCheck0, kEvCheck1, kEvCopies, kEvRate, kEvTile, kNumEvents };
+
 // Per-device cached probe context (CtxBase, crohost.h): the probe runs on
-// every attach, so allocations and events are created once and reused — only
-// the kernels, copies and compares run per call.
+// every attach, so allocations, the stream and the events are created once
+// and reused, and what is the same in every call (the check kernel's inputs
+// at seed 0 and the tile the host expects) is built and uploaded once — only
+// the kernels, the tile's copy back and the compare run per call.
 struct ProbeCtx : CtxBase {
   long long vram_total = 0, vram_free = 0;  // hipMemGetInfo is sysfs-backed
                                             // and ms-scale: snapshot at init
   float *dA = nullptr, *dB = nullptr, *dD = nullptr;
   float4 *src = nullptr, *dst = nullptr;
   float* sink = nullptr;
+  hipStream_t stream = nullptr;  // hipStreamNonBlocking: a probe neither waits
+                                 // for nor holds up the process's other streams
+  hipEvent_t ev[kNumEvents] = {};
+  float* hD = nullptr;                  // pinned: dD lands here in-stream
+  float refD[CRO_COV_F32_ELEMS] = {0};  // expected tile; calls compare, never write
   char gcn_arch[64] = {0};  // hipGetDeviceProperties costs milliseconds —
                             // queried once, the probe runs per attach
 };
@@ -122,14 +147,38 @@ constexpr unsigned long long kMaxCopyVecs = kBwBytes / sizeof(float4);
 constexpr int kMaxCopyGrid = 1 << 16;
 constexpr int kMaxSinkBlocks = 1024;
 constexpr int kMaxSinkIters = 1 << 16;
+constexpr int kRateBlocks = 1024;  // of 256 threads: 4 waves per SIMD on 256 CUs
+// The two rate windows (struct CroProbeWindows: 0 takes these), and the
+// largest a caller may ask for.  Each default is the shortest of the swept
+// windows (1, 2, 4, 8 launches; 256 to 2048 iterations) whose every reading,
+// back to back and from an idle device, stayed within the band the longest
+// one spans in the same run (profiles/quick_probe_windows_mi355x.md): 8
+// launches ≈0.80 ms (4 launches read up to 3 % low from idle), 1024
+// iterations ≈0.25-0.28 ms (512 read 4 % low from idle).
+constexpr int kDefaultCopyLaunches = 8;
+constexpr int kDefaultBf16Iters = 1024;
+constexpr int kMaxCopyLaunches = 64;
+constexpr int kMaxBf16Iters = 1 << 16;
 
-static void launch_copy(const float4* src, float4* dst, size_t n4, int grid_blocks) {
-  hipLaunchKernelGGL(bw_copy_kernel, dim3(grid_blocks), dim3(kBlock), 0, 0, src, dst, n4);
+static void launch_copy(const float4* src, float4* dst, size_t n4, int grid_blocks,
+                        hipStream_t stream = nullptr) {
+  hipLaunchKernelGGL(bw_copy_kernel, dim3(grid_blocks), dim3(kBlock), 0, stream, src, dst, n4);
 }
 
-// The probe's own copy: the launch whose bytes hbm_gbps is credited for.
+// The probe's own copy, on the context's stream: the launch whose bytes
+// hbm_gbps is credited for.
 static void launch_probe_copy(const ProbeCtx* ctx) {
-  launch_copy(ctx->src, ctx->dst, kBwBytes / sizeof(float4), kBwGrid);
+  launch_copy(ctx->src, ctx->dst, kBwBytes / sizeof(float4), kBwGrid, ctx->stream);
+}
+
+static void launch_probe_check(const ProbeCtx* ctx) {
+  hipLaunchKernelGGL(mfma_f32_check_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->dA, ctx->dB,
+                     ctx->dD, CRO_COV_F32_K);
+}
+
+static void launch_probe_rate(const ProbeCtx* ctx, int iters) {
+  hipLaunchKernelGGL(mfma_bf16_rate_kernel<false>, dim3(kRateBlocks), dim3(256), 0, ctx->stream,
+                     ctx->sink, iters);
 }
 
 // Caller holds ctx->mu and has made `device` current.
@@ -141,9 +190,17 @@ static hipError_t ensure_ctx(ProbeCtx* ctx, int device) {
   TRY(hipMalloc(&ctx->src, kBwBytes));
   TRY(hipMalloc(&ctx->dst, kBwBytes));
   TRY(hipMemset(ctx->src, 0x5a, kBwBytes));
-  TRY(hipMalloc(&ctx->sink, 1024 * sizeof(float)));
-  TRY(hipEventCreate(&ctx->e0));
-  TRY(hipEventCreate(&ctx->e1));
+  TRY(hipMalloc(&ctx->sink, kRateBlocks * sizeof(float)));
+  TRY(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
+  for (hipEvent_t& e : ctx->ev) TRY(hipEventCreate(&e));
+  TRY(hipHostMalloc(&ctx->hD, sizeof(ctx->refD), hipHostMallocDefault));
+  // inputs and expected tile are the coverage stage's at seed 0
+  // (crocoverage.h), the same for every call on every device
+  float hA[16 * CRO_COV_F32_K], hB[CRO_COV_F32_K * 16];
+  cro_cov_make_f32(0, hA, hB);
+  cro_cov_ref_f32(hA, hB, ctx->refD);
+  TRY(hipMemcpy(ctx->dA, hA, sizeof(hA), hipMemcpyHostToDevice));
+  TRY(hipMemcpy(ctx->dB, hB, sizeof(hB), hipMemcpyHostToDevice));
   hipDeviceProp_t prop;
   TRY(hipGetDeviceProperties(&prop, device));
   snprintf(ctx->gcn_arch, sizeof(ctx->gcn_arch), "%s", prop.gcnArchName);
@@ -151,93 +208,121 @@ static hipError_t ensure_ctx(ProbeCtx* ctx, int device) {
   TRY(hipMemGetInfo(&free_b, &total_b));
   ctx->vram_total = (long long)total_b;
   ctx->vram_free = (long long)free_b;
-  // one warm round at init covers kernel-code upload; per-call warms are
-  // off the attach path
-  launch_probe_copy(ctx);
-  hipLaunchKernelGGL(mfma_bf16_rate_kernel<false>, dim3(1024), dim3(256), 0, 0, ctx->sink,
-                     64);
+  // one warm round at init covers kernel-code upload (the fill kernel behind
+  // hipMemsetAsync included); per-call warms are off the attach path.  The
+  // set-up above went through the null stream, which this stream does not
+  // wait for: it is drained before the stream sees its first command.
   TRY(hipDeviceSynchronize());
+  TRY(hipMemsetAsync(ctx->dD, 0xFF, sizeof(ctx->refD), ctx->stream));
+  launch_probe_check(ctx);
+  launch_probe_copy(ctx);
+  launch_probe_rate(ctx, 64);
+  TRY(hipGetLastError());
+  TRY(hipMemcpyAsync(ctx->hD, ctx->dD, sizeof(ctx->refD), hipMemcpyDeviceToHost, ctx->stream));
+  TRY(hipStreamSynchronize(ctx->stream));
   ctx->ready = 1;
   return hipSuccess;
 }
 
-extern "C" int cro_probe_run_opts(int device, const struct CroProbeOpts* opts,
-                                  struct CroProbeResult* out) {
-  memset(out, 0, sizeof(*out));
-  out->ok = 0;
-  double t0 = now_ms();
+// Inside enqueue_and_wait: a HIP error goes back to the caller, with the
+// failing call's text in *what for the message.
+#define STEP(expr)                \
+  do {                            \
+    hipError_t _e = (expr);       \
+    if (_e != hipSuccess) {       \
+      *what = #expr;              \
+      return _e;                  \
+    }                             \
+  } while (0)
 
-  struct CroProbeOpts o;
-  memset(&o, 0, sizeof(o));
-  if (opts) o = *opts;
-  // !(x >= 0) also refuses a NaN
-  if (!(o.hbm_floor_gbps >= 0.0)) return bad_arg(out, "hbm_floor_gbps");
-  if (!(o.bf16_floor_tflops >= 0.0)) return bad_arg(out, "bf16_floor_tflops");
-  if (o.selftest_mode < 0 || o.selftest_mode > 1) return bad_arg(out, "selftest_mode");
-  if (o.selftest_bit < 0 || o.selftest_bit > 31) return bad_arg(out, "selftest_bit");
-  if (o.selftest_elem >= CRO_COV_F32_ELEMS) return bad_arg(out, "selftest_elem");
+// One call's whole submission on the context's stream, then its one wait.
+// *enqueued tells the caller that the stream may hold work of this call.
+static hipError_t enqueue_and_wait(ProbeCtx* ctx, int copy_launches, int bf16_iters,
+                                   bool skip_check, bool* enqueued, const char** what) {
+  hipStream_t st = ctx->stream;
+  *enqueued = true;
+  // poison first: a check kernel that did not run must not pass on the tile
+  // the call before left in dD
+  STEP(hipMemsetAsync(ctx->dD, 0xFF, sizeof(ctx->refD), st));
+  STEP(hipEventRecord(ctx->ev[kEvCheck0], st));
+  if (!skip_check) launch_probe_check(ctx);
+  STEP(hipGetLastError());
+  STEP(hipEventRecord(ctx->ev[kEvCheck1], st));
+  for (int i = 0; i < copy_launches; ++i) launch_probe_copy(ctx);
+  STEP(hipGetLastError());
+  STEP(hipEventRecord(ctx->ev[kEvCopies], st));
+  launch_probe_rate(ctx, bf16_iters);
+  STEP(hipGetLastError());
+  STEP(hipEventRecord(ctx->ev[kEvRate], st));
+  STEP(hipMemcpyAsync(ctx->hD, ctx->dD, sizeof(ctx->refD), hipMemcpyDeviceToHost, st));
+  STEP(hipEventRecord(ctx->ev[kEvTile], st));
+  STEP(hipEventSynchronize(ctx->ev[kEvTile]));
+  return hipSuccess;
+}
+
+#undef STEP
+
+// The probe at given windows.  `o` and the windows are validated by the two
+// entries below; t0 is the host clock at the entry.
+static int run_pipeline(int device, const struct CroProbeOpts& o, int copy_launches,
+                        int bf16_iters, bool skip_check, struct CroProbeResult* out, double t0) {
   const double hbm_floor = o.hbm_floor_gbps > 0.0 ? o.hbm_floor_gbps : 500.0;
   const double bf16_floor = o.bf16_floor_tflops > 0.0 ? o.bf16_floor_tflops : 100.0;
 
   std::unique_lock<std::mutex> lock;
   ProbeCtx* ctx = enter_device(g_ctx, device, lock, out->msg, sizeof(out->msg));
   if (ctx == nullptr) return -1;
-
-  // -- exact f32 MFMA ------------------------------------------------------
-  // inputs and expected tile are the coverage stage's at seed 0 (crocoverage.h)
-  out->t_setup_ms = now_ms() - t0;
-  t0 = now_ms();
-  float hA[16 * CRO_COV_F32_K], hB[CRO_COV_F32_K * 16];
-  float hD[CRO_COV_F32_ELEMS], refD[CRO_COV_F32_ELEMS];
-  cro_cov_make_f32(0, hA, hB);
   CHECK(ensure_ctx(ctx, device));
   snprintf(out->gcn_arch, sizeof(out->gcn_arch), "%s", ctx->gcn_arch);
   out->vram_total = ctx->vram_total;
   out->vram_free = ctx->vram_free;
-  CHECK(hipMemcpy(ctx->dA, hA, sizeof(hA), hipMemcpyHostToDevice));
-  CHECK(hipMemcpy(ctx->dB, hB, sizeof(hB), hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(mfma_f32_check_kernel, dim3(1), dim3(64), 0, 0, ctx->dA, ctx->dB, ctx->dD,
-                     CRO_COV_F32_K);
-  CHECK(hipGetLastError());
-  CHECK(hipMemcpy(hD, ctx->dD, sizeof(hD), hipMemcpyDeviceToHost));
-  cro_cov_ref_f32(hA, hB, refD);
+  out->t_setup_ms = now_ms() - t0;
+
+  bool enqueued = false;
+  const char* what = "";
+  const hipError_t e = enqueue_and_wait(ctx, copy_launches, bf16_iters, skip_check, &enqueued,
+                                        &what);
+  if (e != hipSuccess) {
+    // the next caller must find neither the events nor the pinned tile in
+    // flight: drain what was enqueued before the slot's mutex is released
+    if (enqueued) (void)hipStreamSynchronize(ctx->stream);
+    snprintf(out->msg, sizeof(out->msg), "%s failed: %s", what, hipGetErrorString(e));
+    return -1;
+  }
+
+  // -- exact f32 MFMA ------------------------------------------------------
+  const float* want = ctx->refD;
+  float flipped[CRO_COV_F32_ELEMS];
   if (o.selftest_mode == 1) {
     // self-test, for tests only: one bit of one expected element is flipped,
-    // so the exact gate must fire on data alone (as coverage.hip's mode 1)
+    // so the exact gate must fire on data alone (as coverage.hip's mode 1).
+    // The flip is made in this call's copy; the cached tile stays as it is.
+    memcpy(flipped, ctx->refD, sizeof(flipped));
     uint32_t u;
-    memcpy(&u, &refD[o.selftest_elem], sizeof(u));
+    memcpy(&u, &flipped[o.selftest_elem], sizeof(u));
     u ^= 1u << o.selftest_bit;
-    memcpy(&refD[o.selftest_elem], &u, sizeof(u));
+    memcpy(&flipped[o.selftest_elem], &u, sizeof(u));
+    want = flipped;
   }
-  out->mfma_f32_exact = (memcmp(hD, refD, sizeof(hD)) == 0) ? 1 : 0;
+  out->mfma_f32_exact = (memcmp(ctx->hD, want, sizeof(flipped)) == 0) ? 1 : 0;
 
-  out->t_mfma_ms = now_ms() - t0;
-  t0 = now_ms();
-  // -- HBM bandwidth -------------------------------------------------------
-  // 256 MiB src + dst from the cached context (2 GiB of traffic per
-  // measurement — ample signal without putting hipMalloc on the
-  // attach-latency path or pinning more of the 288 GB than a gate needs)
-  const int reps = 8;
   float ms = 0.f;
-  const auto copies = [&] {
-    for (int i = 0; i < reps; ++i) launch_probe_copy(ctx);
-  };
-  CHECK(timed_ms(*ctx, &ms, copies));
-  out->hbm_gbps = (double)(2.0 * kBwBytes * reps) / (ms * 1e6);
-
-  out->t_bw_ms = now_ms() - t0;
-  t0 = now_ms();
+  CHECK(hipEventElapsedTime(&ms, ctx->ev[kEvCheck0], ctx->ev[kEvCheck1]));
+  out->t_mfma_ms = ms;
+  // -- HBM bandwidth -------------------------------------------------------
+  // 256 MiB src + dst from the cached context (512 MiB of traffic per launch,
+  // copy_launches of them per measurement — ample signal without putting
+  // hipMalloc on the attach-latency path or pinning more of the 288 GB than a
+  // gate needs)
+  CHECK(hipEventElapsedTime(&ms, ctx->ev[kEvCheck1], ctx->ev[kEvCopies]));
+  out->hbm_gbps = (double)(2.0 * kBwBytes * copy_launches) / (ms * 1e6);
+  out->t_bw_ms = ms;
   // -- bf16 MFMA rate ------------------------------------------------------
-  const int blocks = 1024, iters = 2048;
-  const auto bf16_rate = [&] {
-    hipLaunchKernelGGL(mfma_bf16_rate_kernel<false>, dim3(blocks), dim3(256), 0, 0, ctx->sink,
-                       iters);
-  };
-  CHECK(timed_ms(*ctx, &ms, bf16_rate));
-  double waves = (double)blocks * 256.0 / 64.0;
-  double flops = waves * 4.0 * (double)iters * 2.0 * 32.0 * 32.0 * 16.0;
+  CHECK(hipEventElapsedTime(&ms, ctx->ev[kEvCopies], ctx->ev[kEvRate]));
+  double waves = (double)kRateBlocks * 256.0 / 64.0;
+  double flops = waves * 4.0 * (double)bf16_iters * 2.0 * 32.0 * 32.0 * 16.0;
   out->bf16_tflops = flops / (ms * 1e9);
-  out->t_bf16_ms = now_ms() - t0;
+  out->t_bf16_ms = ms;
 
   // gates: exact MFMA is hard; bandwidth/rate are loose floors so a busy or
   // power-capped chip never false-fails
@@ -256,6 +341,49 @@ extern "C" int cro_probe_run_opts(int device, const struct CroProbeOpts* opts,
   out->ok = 1;
   snprintf(out->msg, sizeof(out->msg), "ok");
   return 0;
+}
+
+extern "C" int cro_probe_run_opts(int device, const struct CroProbeOpts* opts,
+                                  struct CroProbeResult* out) {
+  memset(out, 0, sizeof(*out));
+  out->ok = 0;
+  const double t0 = now_ms();
+
+  struct CroProbeOpts o;
+  memset(&o, 0, sizeof(o));
+  if (opts) o = *opts;
+  // !(x >= 0) also refuses a NaN
+  if (!(o.hbm_floor_gbps >= 0.0)) return bad_arg(out, "hbm_floor_gbps");
+  if (!(o.bf16_floor_tflops >= 0.0)) return bad_arg(out, "bf16_floor_tflops");
+  if (o.selftest_mode < 0 || o.selftest_mode > 1) return bad_arg(out, "selftest_mode");
+  if (o.selftest_bit < 0 || o.selftest_bit > 31) return bad_arg(out, "selftest_bit");
+  if (o.selftest_elem >= CRO_COV_F32_ELEMS) return bad_arg(out, "selftest_elem");
+  return run_pipeline(device, o, kDefaultCopyLaunches, kDefaultBf16Iters, false, out, t0);
+}
+
+// The same pipeline with the caller's rate windows and the floors at their
+// defaults: how the default windows were chosen
+// (profiles/quick_probe_windows_mi355x.md), and a seam for tests.
+extern "C" int cro_probe_run_windows(int device, const struct CroProbeWindows* w,
+                                     struct CroProbeResult* out) {
+  memset(out, 0, sizeof(*out));
+  out->ok = 0;
+  const double t0 = now_ms();
+
+  struct CroProbeWindows win;
+  memset(&win, 0, sizeof(win));
+  if (w) win = *w;
+  if (win.copy_launches < 0 || win.copy_launches > kMaxCopyLaunches)
+    return bad_arg(out, "copy_launches");
+  if (win.bf16_iters < 0 || win.bf16_iters > kMaxBf16Iters) return bad_arg(out, "bf16_iters");
+  if (win.skip_check_launch < 0 || win.skip_check_launch > 1)
+    return bad_arg(out, "skip_check_launch");
+  if (win.reserved < 0) return bad_arg(out, "reserved");
+  struct CroProbeOpts o;
+  memset(&o, 0, sizeof(o));
+  return run_pipeline(device, o, win.copy_launches ? win.copy_launches : kDefaultCopyLaunches,
+                      win.bf16_iters ? win.bf16_iters : kDefaultBf16Iters,
+                      win.skip_check_launch == 1, out, t0);
 }
 
 extern "C" int cro_probe_run(int device, struct CroProbeResult* out) {
@@ -338,12 +466,15 @@ extern "C" int cro_probe_bw_selfcheck(int device, unsigned long long* n_bad,
   if (ctx == nullptr) return -1;
   const auto copy_once = [&]() -> hipError_t {
     TRY(ensure_ctx(ctx, device));
-    TRY(hipMemset(ctx->dst, 0, kBwBytes));
+    TRY(hipMemsetAsync(ctx->dst, 0, kBwBytes, ctx->stream));
     launch_probe_copy(ctx);
     TRY(hipGetLastError());
-    return hipDeviceSynchronize();
+    return hipSuccess;
   };
-  if (copy_once() != hipSuccess) return -1;
+  // whatever was enqueued is drained before dst is read or the mutex released
+  const hipError_t enq = copy_once();
+  const hipError_t done = ctx->stream ? hipStreamSynchronize(ctx->stream) : hipSuccess;
+  if (enq != hipSuccess || done != hipSuccess) return -1;
   const size_t chunk = (size_t)32 << 20;
   std::vector<unsigned char> host(chunk);
   for (size_t off = 0; off < kBwBytes; off += chunk) {

@@ -44,6 +44,17 @@ class CroProbeOpts(ctypes.Structure):
     ]
 
 
+class CroProbeWindows(ctypes.Structure):
+    """Mirror of ``struct CroProbeWindows`` (cro_amd/hip/croprobe.h)."""
+
+    _fields_ = [
+        ("copy_launches", ctypes.c_int),
+        ("bf16_iters", ctypes.c_int),
+        ("skip_check_launch", ctypes.c_int),
+        ("reserved", ctypes.c_int),
+    ]
+
+
 class CroIntegrityOpts(ctypes.Structure):
     """Mirror of ``struct CroIntegrityOpts`` (cro_amd/hip/croprobe.h)."""
 
@@ -207,6 +218,10 @@ def load_library(required: Optional[bool] = None) -> Optional[ctypes.CDLL]:
         ctypes.c_int, ctypes.POINTER(CroProbeOpts), ctypes.POINTER(CroProbeResult),
     ]
     lib.cro_probe_run_opts.restype = ctypes.c_int
+    lib.cro_probe_run_windows.argtypes = [
+        ctypes.c_int, ctypes.POINTER(CroProbeWindows), ctypes.POINTER(CroProbeResult),
+    ]
+    lib.cro_probe_run_windows.restype = ctypes.c_int
     f32p = ctypes.POINTER(ctypes.c_float)
     lib.cro_probe_mfma_f32.argtypes = [ctypes.c_int, f32p, f32p, f32p, ctypes.c_int]
     lib.cro_probe_mfma_f32.restype = ctypes.c_int
@@ -357,6 +372,23 @@ def run_probe(device: int = 0, **opts) -> dict:
         rc = lib.cro_probe_run_opts(device, ctypes.byref(c_opts), ctypes.byref(res))
     else:
         rc = lib.cro_probe_run(device, ctypes.byref(res))
+    return _result_dict(res, rc)
+
+
+def run_probe_windows(device: int = 0, copy_launches: int = 0, bf16_iters: int = 0,
+                      skip_check_launch: int = 0) -> dict:
+    """The quick probe's pipeline at the caller's rate windows (``struct
+    CroProbeWindows``; zero takes the library default, which is what
+    ``run_probe`` runs at), with the floors at their defaults.
+    ``skip_check_launch`` is for tests: the check kernel is left out, so the
+    exact gate must fail on the poisoned tile."""
+    lib = load_library(required=True)
+    windows = CroProbeWindows(
+        copy_launches=int(copy_launches), bf16_iters=int(bf16_iters),
+        skip_check_launch=int(skip_check_launch),
+    )
+    res = CroProbeResult()
+    rc = lib.cro_probe_run_windows(device, ctypes.byref(windows), ctypes.byref(res))
     return _result_dict(res, rc)
 
 
