@@ -97,6 +97,18 @@ def add_probe_arguments(p: argparse.ArgumentParser) -> None:
                    help="coherence probe: fail when fewer than this fraction of "
                    "the device's CUs were reached (0 = off: coverage is "
                    "reported, only data gates)")
+    p.add_argument("--probe-movement", choices=["off", "on"],
+                   default=env("CRO_PROBE_MOVEMENT", "off"),
+                   help="on: additionally run exact checks of the cross-lane paths (DPP, "
+                   "ds_swizzle / ds_permute / ds_bpermute, readlane / writelane, the "
+                   "half-wave swaps), the transposed LDS reads and LDS-DMA on every CU "
+                   "and SIMD, at either level; a failure names the check, variant, lane "
+                   "and register and the XCD, CU and SIMD")
+    p.add_argument("--probe-movement-min-cu-fraction", type=float,
+                   default=float(env("CRO_PROBE_MOVEMENT_MIN_CU_FRACTION", "0")),
+                   help="movement probe: fail when fewer than this fraction of "
+                   "the device's CUs were reached (0 = off: coverage is "
+                   "reported, only data gates)")
 
 
 def select_probe_fn(args):
@@ -111,6 +123,9 @@ def select_probe_fn(args):
     if getattr(args, "probe_coherence", "off") == "on":
         stages.update(coherence=True,
                       coherence_min_cu_fraction=args.probe_coherence_min_cu_fraction)
+    if getattr(args, "probe_movement", "off") == "on":
+        stages.update(movement=True,
+                      movement_min_cu_fraction=args.probe_movement_min_cu_fraction)
     return make_probe_fn(
         args.probe_level,
         vram_bytes=args.probe_vram_mib << 20,
@@ -124,9 +139,9 @@ def select_probe_fn(args):
 
 def drop_unavailable_probe_stages(args, log) -> bool:
     """An optional probe stage with a library of its own (--probe-formats,
-    --probe-coherence) that is on but whose library is not on this node: warn,
-    switch the stage off in ``args`` and go on without it.  True when one was
-    switched off."""
+    --probe-coherence, --probe-movement) that is on but whose library is not
+    on this node: warn, switch the stage off in ``args`` and go on without it.
+    True when one was switched off."""
     dropped = False
     if getattr(args, "probe_formats", "off") == "on":
         lib = None
@@ -155,6 +170,20 @@ def drop_unavailable_probe_stages(args, log) -> bool:
         else:
             log.warning("gfx950 coherence probe library unavailable; coherence stage disabled")
             args.probe_coherence = "off"
+            dropped = True
+    if getattr(args, "probe_movement", "off") == "on":
+        lib = None
+        try:
+            from ..nodeops.movement import load_movement_library
+
+            lib = load_movement_library(required=False)
+        except Exception:
+            pass
+        if lib is not None:
+            log.info("health probe data-movement stage: on")
+        else:
+            log.warning("gfx950 data-movement probe library unavailable; movement stage disabled")
+            args.probe_movement = "off"
             dropped = True
     return dropped
 

@@ -518,6 +518,26 @@ class ComposableResourceReconciler(Reconciler):
                     f"gfx950 health probe failed: coherence stage {test} {where} "
                     f"block={coherence.get('bad_block')} cus_bad={coherence.get('cus_bad')}: {probe}"
                 )
+            movement = probe.get("movement")
+            if isinstance(movement, dict) and not movement.get("ok", True):
+                # data-movement stage: the check, which variant, lane and
+                # register received the wrong word, then where on the chip
+                from ..nodeops.movement import describe_first_bad
+
+                test = movement.get("failed_test") or (
+                    "coverage" if movement.get("rc") == -37 else "unknown"
+                )
+                self.metrics.probe_movement_failures_total.labels(test=test).inc()
+                what = ""
+                if movement.get("failed_test"):
+                    what = describe_first_bad(test, int(movement.get("first_bad", 0))) + " "
+                raise FabricError(
+                    f"gfx950 health probe failed: movement stage {test} {what}"
+                    f"xcd={movement.get('xcd')} se={movement.get('se')} "
+                    f"cu={movement.get('cu')} simd={movement.get('simd')} "
+                    f"bits_bad=0x{int(movement.get('bits_bad', 0)):08x} "
+                    f"cus_bad={movement.get('cus_bad')}: {probe}"
+                )
             integrity = probe.get("integrity")
             if isinstance(integrity, dict) and not integrity.get("ok", True):
                 # deep level: lead with what an operator needs to act on —
@@ -562,6 +582,14 @@ class ComposableResourceReconciler(Reconciler):
                     f"/{coherence.get('cus_expected', 0)} CUs,"
                     f" {coherence.get('pairs_checked', 0)} pairs,"
                     f" {coherence.get('gpu_ms', 0):.1f} ms"
+                )
+            movement = probe.get("movement")
+            if isinstance(movement, dict):
+                probe_note += (
+                    f"; movement: {movement.get('cus_seen', 0)}"
+                    f"/{movement.get('cus_expected', 0)} CUs,"
+                    f" {movement.get('simds_seen', 0)} SIMDs,"
+                    f" {movement.get('gpu_ms', 0):.1f} ms"
                 )
             integrity = probe.get("integrity")
             if isinstance(integrity, dict):

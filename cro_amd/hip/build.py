@@ -81,6 +81,15 @@ COHERENCE_HEADERS = [
     COVERAGE_HEADER,  # for cro_cov_cu_key and cro_cov_decode
 ]
 COHERENCE_OUT = os.path.join(HIP_DIR, "libcrocoherence.so")
+# data-movement probe stage (cross-lane, transposed LDS reads, LDS-DMA): a
+# library of its own as well (the lists above are pinned by their tests)
+MOVEMENT_SRC = os.path.join(HIP_DIR, "movement.hip")
+MOVEMENT_HEADERS = [
+    os.path.join(HIP_DIR, "cromovement.h"),
+    os.path.join(HIP_DIR, "crohost.h"),
+    COVERAGE_HEADER,  # for cro_cov_cu_key and cro_cov_decode
+]
+MOVEMENT_OUT = os.path.join(HIP_DIR, "libcromovement.so")
 AGENT_SRC = os.path.join(AGENT_DIR, "croagent.cpp")
 AGENT_OUT = os.path.join(AGENT_DIR, "croagent")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -157,6 +166,16 @@ def build_coherence(force: bool = False) -> str:
     return COHERENCE_OUT
 
 
+def build_movement(force: bool = False) -> str:
+    """libcromovement.so: the data-movement probe stage (movement.hip)."""
+    if force or _stale(MOVEMENT_OUT, [MOVEMENT_SRC] + MOVEMENT_HEADERS):
+        subprocess.run(
+            [HIPCC, *DEVICE_FLAGS, "-fPIC", "-shared", MOVEMENT_SRC, "-o", MOVEMENT_OUT],
+            check=True,
+        )
+    return MOVEMENT_OUT
+
+
 def build_agent(force: bool = False) -> str:
     """croagent: the native node-agent CLI (links libcroprobe; loads
     libcroscrub.so, libcroldsscrub.so, libcroregscrub.so, libcroformats.so and
@@ -194,4 +213,5 @@ if __name__ == "__main__":
     print(build_lds_scrub(force="--force" in sys.argv))
     print(build_formats(force="--force" in sys.argv))
     print(build_coherence(force="--force" in sys.argv))
+    print(build_movement(force="--force" in sys.argv))
     print(build_reg_scrub(force="--force" in sys.argv))

@@ -96,6 +96,14 @@ class Metrics:
             "optional CU-coverage floor)",
             ["test"],
         )
+        self.probe_movement_failures_total = Counter(
+            "cro_probe_movement_failures_total",
+            "Attaches refused by the probe's data-movement stage, by the check "
+            "that failed (dpp, swizzle, bpermute, permlane_swap, readlane, "
+            "lds_tr16, lds_tr8, lds_tr4, lds_tr6, lds_dma; coverage for the "
+            "optional CU-coverage floor)",
+            ["test"],
+        )
         self.scrub_failures_total = Counter(
             "cro_scrub_failures_total",
             "Scrubs before drain that did not pass, by reason (residue: words "
@@ -131,6 +139,7 @@ class Metrics:
                 cls._singleton.probe_compute_failures_total,
                 cls._singleton.probe_formats_failures_total,
                 cls._singleton.probe_coherence_failures_total,
+                cls._singleton.probe_movement_failures_total,
                 cls._singleton.scrub_failures_total,
                 cls._singleton.scrub_seconds,
                 cls._singleton.scrub_bytes_total,

@@ -929,7 +929,8 @@ def make_probe_fn(level: str = "quick", vram_bytes: int = 0, link_bytes: int = 0
                   link_floor_gbps: float = 0.0, seed: int = 0, compute: bool = False,
                   compute_min_cu_fraction: float = 0.0, formats: bool = False,
                   formats_min_cu_fraction: float = 0.0, coherence: bool = False,
-                  coherence_min_cu_fraction: float = 0.0):
+                  coherence_min_cu_fraction: float = 0.0, movement: bool = False,
+                  movement_min_cu_fraction: float = 0.0):
     """AmdNodeOps probe hook for a probe level.
 
     ``quick`` is the rate/matrix-pipe gate.  ``deep`` runs it first and, only
@@ -948,12 +949,17 @@ def make_probe_fn(level: str = "quick", vram_bytes: int = 0, link_bytes: int = 0
 
     ``coherence=True`` adds the coherence stage (nodeops/coherence.py: the
     atomic units and cross-CU visibility) after the formats stage and before
-    integrity, in the same way; its result nests under ``"coherence"``.  The
-    order is quick, compute, formats, coherence, integrity.
+    integrity, in the same way; its result nests under ``"coherence"``.
+
+    ``movement=True`` adds the data-movement stage (nodeops/movement.py: the
+    cross-lane, transposed-LDS-read and LDS-DMA paths) after the coherence
+    stage and before integrity, in the same way; its result nests under
+    ``"movement"``.  The order is quick, compute, formats, coherence,
+    movement, integrity.
     """
     if level not in PROBE_LEVELS:
         raise ValueError(f"unknown probe level {level!r} (expected one of {PROBE_LEVELS})")
-    if level == "quick" and not compute and not formats and not coherence:
+    if level == "quick" and not compute and not formats and not coherence and not movement:
         return probe_fn_for_nodeops
 
     def staged_probe(gpu) -> dict:
@@ -988,6 +994,15 @@ def make_probe_fn(level: str = "quick", vram_bytes: int = 0, link_bytes: int = 0
                 result["ok"] = False
                 result["msg"] = stage.get("msg", "coherence probe failed")
                 return result
+        if movement:
+            from .movement import run_movement
+
+            stage = run_movement(dev, seed=seed, min_cu_fraction=movement_min_cu_fraction)
+            result["movement"] = stage
+            if not stage.get("ok"):
+                result["ok"] = False
+                result["msg"] = stage.get("msg", "movement probe failed")
+                return result
         if level == "deep":
             integrity = run_integrity(
                 dev, vram_bytes=vram_bytes, link_bytes=link_bytes, seed=seed,
@@ -1005,6 +1020,8 @@ def make_probe_fn(level: str = "quick", vram_bytes: int = 0, link_bytes: int = 0
         staged_probe.formats = True
     if coherence:
         staged_probe.coherence = True
+    if movement:
+        staged_probe.movement = True
     return staged_probe
 
 
@@ -1035,6 +1052,15 @@ def _coherence_argv(coherence, coherence_min_cu_fraction) -> list:
     return argv
 
 
+def _movement_argv(movement, movement_min_cu_fraction) -> list:
+    if not movement:
+        return []
+    argv = ["--movement"]
+    if movement_min_cu_fraction:
+        argv += ["--movement-min-cu-fraction", str(float(movement_min_cu_fraction))]
+    return argv
+
+
 def _deep_argv(level: str, vram_mib, link_mib, link_floor_gbps) -> list:
     if level == "quick":
         return []
@@ -1054,14 +1080,16 @@ def probe_via_exec(execer, node: str, gpu, argv_prefix=None, level: str = "quick
                    vram_mib=None, link_mib=None, link_floor_gbps=0, compute: bool = False,
                    compute_min_cu_fraction=0, formats: bool = False,
                    formats_min_cu_fraction=0, coherence: bool = False,
-                   coherence_min_cu_fraction=0) -> dict:
+                   coherence_min_cu_fraction=0, movement: bool = False,
+                   movement_min_cu_fraction=0) -> dict:
     """Health probe through the node agent (``croagent probe --bdf``) — the
     cluster shape where controllers run off-node and reach hardware only
     through the NodeExec seam.  Returns the same dict shape as run_probe
     (at level ``deep``: as make_probe_fn("deep"), via ``croagent probe
     --deep`` and the size options given; with ``compute``: as
     make_probe_fn(..., compute=True), via ``--compute``; with ``formats``:
-    via ``--formats``; with ``coherence``: via ``--coherence``).
+    via ``--formats``; with ``coherence``: via ``--coherence``; with
+    ``movement``: via ``--movement``).
 
     ``argv_prefix`` wraps the command for the container-driver arm (e.g.
     ``["chroot", "/run/amdgpu-driver"]`` so the probe runs against the
@@ -1075,6 +1103,7 @@ def probe_via_exec(execer, node: str, gpu, argv_prefix=None, level: str = "quick
     argv += _compute_argv(compute, compute_min_cu_fraction)
     argv += _formats_argv(formats, formats_min_cu_fraction)
     argv += _coherence_argv(coherence, coherence_min_cu_fraction)
+    argv += _movement_argv(movement, movement_min_cu_fraction)
     rc, out, err = execer.run(node, argv, timeout=300)
     if rc != 0 and not out.strip():
         return {"ok": False, "rc": rc, "msg": err.strip() or "croagent probe failed"}
@@ -1088,7 +1117,8 @@ def make_exec_probe_fn(execer, node: str, argv_prefix_fn=None, level: str = "qui
                        vram_mib=None, link_mib=None, link_floor_gbps=0, compute: bool = False,
                        compute_min_cu_fraction=0, formats: bool = False,
                        formats_min_cu_fraction=0, coherence: bool = False,
-                       coherence_min_cu_fraction=0):
+                       coherence_min_cu_fraction=0, movement: bool = False,
+                       movement_min_cu_fraction=0):
     """AmdNodeOps probe hook bound to a NodeExec (local or remote agent).
 
     ``argv_prefix_fn()`` is resolved per probe so a driver-mode change
@@ -1103,6 +1133,8 @@ def make_exec_probe_fn(execer, node: str, argv_prefix_fn=None, level: str = "qui
         stages.update(formats=True, formats_min_cu_fraction=formats_min_cu_fraction)
     if coherence:
         stages.update(coherence=True, coherence_min_cu_fraction=coherence_min_cu_fraction)
+    if movement:
+        stages.update(movement=True, movement_min_cu_fraction=movement_min_cu_fraction)
 
     def probe(gpu):
         prefix = argv_prefix_fn() if argv_prefix_fn else None
