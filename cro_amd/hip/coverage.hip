@@ -322,8 +322,7 @@ struct CovCtx : CtxBase {
   float hE32[CRO_COV_F32_ELEMS];
   int hE8[CRO_COV_I8_ELEMS];
   float hE16[CRO_COV_BF16_ELEMS];
-  CroCoverageRecord* d_records = nullptr;
-  size_t records_cap = 0;
+  RecordBuf<CroCoverageRecord> records;
 };
 CovCtx g_cctx[kMaxDevices];
 
@@ -396,15 +395,9 @@ int prepare(CovCtx* ctx, int device, uint32_t seed, CroComputeResult* out) {
   return 0;
 }
 
-// The record buffer holds at least n records afterwards.
-int reserve_records(CovCtx* ctx, size_t n, CroComputeResult* out) {
-  if (ctx->records_cap >= n) return 0;
-  if (ctx->d_records) (void)hipFree(ctx->d_records);
-  ctx->d_records = nullptr;
-  ctx->records_cap = 0;
-  CHECK(hipMalloc(&ctx->d_records, n * sizeof(CroCoverageRecord)));
-  ctx->records_cap = n;
-  return 0;
+// The stage's aggregate as crohost.h's templates call it.
+void aggregate(const CroCoverageRecord* records, size_t n, CroCoverageAgg* out) {
+  cro_coverage_aggregate(records, n, 0, out);
 }
 
 void set_inputs(const CovCtx* ctx, CovParams* p) {
@@ -461,8 +454,7 @@ int run_compute(int device, const CroComputeOpts* opts, const CallerTiles& tiles
   const int grid = o.grid_blocks ? o.grid_blocks : ctx->cus;
   if (grid < 1) return bad_arg(out, "device reports no compute units");
   const size_t per_round = (size_t)grid * kWaves;
-  const size_t n_max = per_round * (size_t)max_rounds;
-  if (reserve_records(ctx, n_max, out) != 0) return -1;
+  CHECK(ctx->records.reserve(per_round * (size_t)max_rounds));
   out->cus_expected = ctx->cus;
   out->grid_blocks = grid;
   out->lds_bytes = lds_bytes;
@@ -503,47 +495,19 @@ int run_compute(int device, const CroComputeOpts* opts, const CallerTiles& tiles
     p.E16 = ctx->dX16;
   }
 
-  std::vector<CroCoverageRecord> records(n_max);
-  CHECK(hipMemset(ctx->d_records, 0, n_max * sizeof(CroCoverageRecord)));
-  int rounds = 0;
-  double gpu_ms = 0.0;
-  for (;;) {
-    p.records = ctx->d_records + (size_t)rounds * per_round;
-    const auto one_round = [&] {
-      if (plant)
-        hipLaunchKernelGGL(coverage_kernel<true>, dim3(grid), dim3(kBlock), (size_t)lds_bytes, 0,
-                           p);
-      else
-        hipLaunchKernelGGL(coverage_kernel<false>, dim3(grid), dim3(kBlock), (size_t)lds_bytes,
-                           0, p);
-    };
-    float ms = 0.f;
-    CHECK(timed_ms(*ctx, &ms, one_round));
-    gpu_ms += ms;
-    CHECK(hipMemcpy(records.data() + (size_t)rounds * per_round, p.records,
-                     per_round * sizeof(CroCoverageRecord), hipMemcpyDeviceToHost));
-    ++rounds;
-    cro_coverage_aggregate(records.data(), (size_t)rounds * per_round, ctx->cus, &out->agg);
-    const bool covered =
-        out->agg.cus_seen >= ctx->cus && out->agg.simds_seen >= 4 * out->agg.cus_seen;
-    if (out->agg.waves_bad || covered || rounds >= max_rounds) break;
-  }
-  out->rounds = rounds;
-  out->gpu_ms = gpu_ms;
-  const size_t n = (size_t)rounds * per_round;
-  if (records_out && max_records > 0) {
-    const size_t m = n < (size_t)max_records ? n : (size_t)max_records;
-    memcpy(records_out, records.data(), m * sizeof(CroCoverageRecord));
-  }
-  const CroCoverageAgg& a = out->agg;
-  if (a.waves_run != n) {
-    // a wave that never wrote its record: the launch did not run to the end
-    snprintf(out->msg, sizeof(out->msg), "%llu of %zu waves reported", a.waves_run, n);
+  const auto launch = [&](CroCoverageRecord* d_round) {
+    p.records = d_round;
+    if (plant)
+      hipLaunchKernelGGL(coverage_kernel<true>, dim3(grid), dim3(kBlock), (size_t)lds_bytes, 0, p);
+    else
+      hipLaunchKernelGGL(coverage_kernel<false>, dim3(grid), dim3(kBlock), (size_t)lds_bytes, 0,
+                         p);
+  };
+  if (run_rounds(*ctx, ctx->records.d, ctx->cus, per_round, max_rounds, launch, aggregate, out,
+                 records_out, max_records) != 0)
     return -1;
-  }
+  const CroCoverageAgg& a = out->agg;
   if (a.waves_bad) {
-    out->first_bad_round = (int)((size_t)a.first_bad_index / per_round);
-    out->first_bad_record = (int)((size_t)a.first_bad_index % per_round);
     snprintf(out->failed_test, sizeof(out->failed_test), "%s",
              cro_cov_test_name(a.first_fail_mask));
     snprintf(out->msg, sizeof(out->msg),
@@ -553,15 +517,7 @@ int run_compute(int device, const CroComputeOpts* opts, const CallerTiles& tiles
              a.waves_bad, a.waves_run, a.cus_bad);
     return -30;
   }
-  if (o.min_cu_fraction > 0.0 && (double)a.cus_seen < o.min_cu_fraction * (double)ctx->cus) {
-    snprintf(out->msg, sizeof(out->msg),
-             "coverage %d of %d CUs after %d rounds is below the floor %.3f", a.cus_seen,
-             ctx->cus, rounds, o.min_cu_fraction);
-    return -31;
-  }
-  out->ok = 1;
-  snprintf(out->msg, sizeof(out->msg), "ok");
-  return 0;
+  return coverage_floor(out, ctx->cus, o.min_cu_fraction, -31);
 }
 
 int run_lds_dump(int device, int grid_blocks, int lds_bytes, uint32_t seed, int pass,
@@ -581,7 +537,7 @@ int run_lds_dump(int device, int grid_blocks, int lds_bytes, uint32_t seed, int 
   CovCtx* ctx = enter_device(g_cctx, device, lock, out->msg, sizeof(out->msg));
   if (ctx == nullptr) return -1;
   if (prepare(ctx, device, seed, out) != 0) return -1;
-  if (reserve_records(ctx, (size_t)grid_blocks * kWaves, out) != 0) return -1;
+  CHECK(ctx->records.reserve((size_t)grid_blocks * kWaves));
   const size_t dump_bytes = (size_t)grid_blocks * lds_bytes;
   DevBuf<uint32_t> d_dump;
   DevBuf<unsigned int> d_guard;
@@ -592,7 +548,7 @@ int run_lds_dump(int device, int grid_blocks, int lds_bytes, uint32_t seed, int 
 
   CovParams p;
   set_inputs(ctx, &p);
-  p.records = ctx->d_records;  // the kernel returns before it writes one
+  p.records = ctx->records.d;  // the kernel returns before it writes one
   p.lds_words = lds_words;
   p.iters = 1;
   p.seed = seed;
@@ -615,14 +571,6 @@ int run_lds_dump(int device, int grid_blocks, int lds_bytes, uint32_t seed, int 
   return 0;
 }
 
-void clear_result(CroComputeResult* out) {
-  memset(out, 0, sizeof(*out));
-  out->first_bad_round = out->first_bad_record = -1;
-  out->agg.first_bad_index = -1;
-  out->agg.xcd = out->agg.se = out->agg.sh = out->agg.cu = out->agg.simd = -1;
-  out->agg.first_bad = ~0u;
-}
-
 }  // namespace
 
 extern "C" int cro_probe_compute_tiles(int device, const struct CroComputeOpts* opts,
@@ -630,7 +578,7 @@ extern "C" int cro_probe_compute_tiles(int device, const struct CroComputeOpts* 
                                        struct CroComputeResult* out,
                                        struct CroCoverageRecord* records_out,
                                        int max_records) {
-  clear_result(out);
+  clear_result(out, aggregate);
   CallerTiles tiles;
   tiles.e32 = e32;
   tiles.e8 = e8;
@@ -655,7 +603,7 @@ extern "C" int cro_probe_compute_lds_dump(int device, int grid_blocks, int lds_b
                                           int plant_bit, unsigned int* host_out,
                                           unsigned int* guard_bad_out) {
   CroComputeResult res;  // for the HIP error text, which this entry does not return
-  clear_result(&res);
+  clear_result(&res, aggregate);
   return run_lds_dump(device, grid_blocks, lds_bytes, seed, pass, plant_elem, plant_span,
                       plant_bit, host_out, guard_bad_out, &res);
 }

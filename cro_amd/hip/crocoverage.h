@@ -102,16 +102,17 @@ static inline CroCoverageLoc cro_cov_decode_key(uint32_t key) {
 }
 
 // -- aggregation ----------------------------------------------------------------
+// The per-wave stages (compute here, matrix formats in croformats.h, data
+// movement in cromovement.h) write records of one layout, CroCoverageRecord's,
+// and aggregate them the same way: one pass in record order into the neutral
+// summary below, from which each stage fills its own Cro*Agg.
 
-enum { CRO_COV_MAX_BAD_KEYS = 8 };
+enum { CRO_COV_MAX_BAD_KEYS = 8, CRO_COV_MAX_MASK_BITS = 32 };
 
-struct CroCoverageAgg {
+struct CroWaveSummary {
   unsigned long long waves_run;  // valid records
   unsigned long long waves_bad;  // records with a non-zero fail mask
-  unsigned long long bad_f32;    // bad waves per test, from the fail mask
-  unsigned long long bad_i8;
-  unsigned long long bad_bf16;
-  unsigned long long bad_lds;
+  unsigned long long bad[CRO_COV_MAX_MASK_BITS];  // bad waves per fail-mask bit
   long long first_bad_index;  // index of the first bad record; -1 = none
   int cus_seen;               // distinct CU keys
   int xcds_seen;
@@ -120,6 +121,7 @@ struct CroCoverageAgg {
   // the first bad wave (lowest record index, i.e. lowest (round, record));
   // -1 / 0 when there is none
   int xcd, se, sh, cu, simd;
+  unsigned int fail_mask;  // OR of every valid record's fail mask
   unsigned int first_fail_mask;
   unsigned int n_bad;
   unsigned int first_bad;
@@ -128,23 +130,35 @@ struct CroCoverageAgg {
   unsigned int bad_cu_keys[CRO_COV_MAX_BAD_KEYS];  // in order of first appearance
 };
 
-// Deterministic: one pass in record order.  cus_expected is carried by the
-// caller's result; the aggregate itself only counts what it saw.
-static inline void cro_coverage_aggregate(const CroCoverageRecord* records, size_t n,
-                                          int cus_expected, CroCoverageAgg* out) {
-  (void)cus_expected;
+static inline void cro_wave_summary_clear(CroWaveSummary* out) {
+  memset(out, 0, sizeof(*out));
+  out->first_bad_index = -1;
+  out->xcd = out->se = out->sh = out->cu = out->simd = -1;
+  out->first_bad = ~0u;
+}
+
+// Deterministic: one pass in record order.
+template <class Record>
+void cro_wave_summarize(const Record* records, size_t n, CroWaveSummary* out) {
+  static_assert(sizeof(Record) == sizeof(CroCoverageRecord) &&
+                    offsetof(Record, xcc_id) == offsetof(CroCoverageRecord, xcc_id) &&
+                    offsetof(Record, hw_id) == offsetof(CroCoverageRecord, hw_id) &&
+                    offsetof(Record, fail_mask) == offsetof(CroCoverageRecord, fail_mask) &&
+                    offsetof(Record, n_bad) == offsetof(CroCoverageRecord, n_bad) &&
+                    offsetof(Record, first_bad) == offsetof(CroCoverageRecord, first_bad) &&
+                    offsetof(Record, bits_bad) == offsetof(CroCoverageRecord, bits_bad) &&
+                    offsetof(Record, valid) == offsetof(CroCoverageRecord, valid) &&
+                    offsetof(Record, reserved) == offsetof(CroCoverageRecord, reserved),
+                "a per-wave stage's record has CroCoverageRecord's layout");
   // compact key: xcd(4) | se(3) | sh(1) | cu(4) = 12 bits
   static const int kKeys = 1 << 12;
   unsigned char simds[kKeys];  // bits 0..3 SIMD seen, bit 7 CU had a bad wave
   unsigned char xcds[16];
   memset(simds, 0, sizeof(simds));
   memset(xcds, 0, sizeof(xcds));
-  memset(out, 0, sizeof(*out));
-  out->first_bad_index = -1;
-  out->xcd = out->se = out->sh = out->cu = out->simd = -1;
-  out->first_bad = ~0u;
+  cro_wave_summary_clear(out);
   for (size_t i = 0; i < n; ++i) {
-    const CroCoverageRecord& r = records[i];
+    const Record& r = records[i];
     if (!r.valid) continue;
     ++out->waves_run;
     const CroCoverageLoc loc = cro_cov_decode(r.xcc_id, r.hw_id);
@@ -156,10 +170,9 @@ static inline void cro_coverage_aggregate(const CroCoverageRecord* records, size
     xcds[loc.xcd] = 1;
     if (!r.fail_mask) continue;
     ++out->waves_bad;
-    if (r.fail_mask & 1u) ++out->bad_f32;
-    if (r.fail_mask & 2u) ++out->bad_i8;
-    if (r.fail_mask & 4u) ++out->bad_bf16;
-    if (r.fail_mask & 8u) ++out->bad_lds;
+    out->fail_mask |= r.fail_mask;
+    for (int t = 0; t < CRO_COV_MAX_MASK_BITS; ++t)
+      if (r.fail_mask & (1u << t)) ++out->bad[t];
     if (!(simds[idx] & 0x80u)) {
       simds[idx] |= 0x80u;
       if (out->cus_bad < CRO_COV_MAX_BAD_KEYS)
@@ -179,6 +192,66 @@ static inline void cro_coverage_aggregate(const CroCoverageRecord* records, size
       out->bits_bad = r.bits_bad;
     }
   }
+}
+
+// Zeroes *out and fills what every stage's aggregate has under the same
+// name; the stage adds its per-test counts and its extras.
+template <class Agg>
+void cro_wave_common(const CroWaveSummary& s, Agg* out) {
+  memset(out, 0, sizeof(*out));
+  out->waves_run = s.waves_run;
+  out->waves_bad = s.waves_bad;
+  out->first_bad_index = s.first_bad_index;
+  out->cus_seen = s.cus_seen;
+  out->xcds_seen = s.xcds_seen;
+  out->simds_seen = s.simds_seen;
+  out->cus_bad = s.cus_bad;
+  out->xcd = s.xcd;
+  out->se = s.se;
+  out->sh = s.sh;
+  out->cu = s.cu;
+  out->simd = s.simd;
+  out->first_fail_mask = s.first_fail_mask;
+  out->n_bad = s.n_bad;
+  out->first_bad = s.first_bad;
+  out->bits_bad = s.bits_bad;
+}
+
+struct CroCoverageAgg {
+  unsigned long long waves_run;  // as CroWaveSummary's
+  unsigned long long waves_bad;
+  unsigned long long bad_f32;  // bad waves per test, from the fail mask
+  unsigned long long bad_i8;
+  unsigned long long bad_bf16;
+  unsigned long long bad_lds;
+  long long first_bad_index;
+  int cus_seen;
+  int xcds_seen;
+  int simds_seen;
+  int cus_bad;
+  int xcd, se, sh, cu, simd;
+  unsigned int first_fail_mask;
+  unsigned int n_bad;
+  unsigned int first_bad;
+  unsigned int bits_bad;
+  int n_bad_cu_keys;
+  unsigned int bad_cu_keys[CRO_COV_MAX_BAD_KEYS];
+};
+
+// Over no records this is the cleared aggregate.  cus_expected is carried by
+// the caller's result; the aggregate itself only counts what it saw.
+static inline void cro_coverage_aggregate(const CroCoverageRecord* records, size_t n,
+                                          int cus_expected, CroCoverageAgg* out) {
+  (void)cus_expected;
+  CroWaveSummary s;
+  cro_wave_summarize(records, n, &s);
+  cro_wave_common(s, out);
+  out->bad_f32 = s.bad[CRO_COV_TEST_F32];
+  out->bad_i8 = s.bad[CRO_COV_TEST_I8];
+  out->bad_bf16 = s.bad[CRO_COV_TEST_BF16];
+  out->bad_lds = s.bad[CRO_COV_TEST_LDS];
+  out->n_bad_cu_keys = s.n_bad_cu_keys;
+  memcpy(out->bad_cu_keys, s.bad_cu_keys, sizeof(out->bad_cu_keys));
 }
 
 // -- inputs and expected tiles ----------------------------------------------------

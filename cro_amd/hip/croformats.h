@@ -484,51 +484,13 @@ struct CroFormatsAgg {
   unsigned int reserved;  // to a multiple of 8 bytes: the flat mirrors have no hole
 };
 
-// Deterministic: one pass in record order.
+// cro_wave_summarize (crocoverage.h); over no records the cleared aggregate.
 static inline void cro_formats_aggregate(const CroFormatsRecord* records, size_t n,
                                          CroFormatsAgg* out) {
-  // compact key: xcd(4) | se(3) | sh(1) | cu(4) = 12 bits
-  static const int kKeys = 1 << 12;
-  unsigned char simds[kKeys];  // bits 0..3 SIMD seen, bit 7 CU had a bad wave
-  unsigned char xcds[16];
-  memset(simds, 0, sizeof(simds));
-  memset(xcds, 0, sizeof(xcds));
-  memset(out, 0, sizeof(*out));
-  out->first_bad_index = -1;
-  out->xcd = out->se = out->sh = out->cu = out->simd = -1;
-  out->first_bad = ~0u;
-  for (size_t i = 0; i < n; ++i) {
-    const CroFormatsRecord& r = records[i];
-    if (!r.valid) continue;
-    ++out->waves_run;
-    const CroCoverageLoc loc = cro_cov_decode(r.xcc_id, r.hw_id);
-    const unsigned idx = (loc.xcd << 8) | ((r.hw_id >> 8) & 0xFFu);
-    if ((simds[idx] & 0x0Fu) == 0) ++out->cus_seen;
-    if (!(simds[idx] & (1u << loc.simd))) ++out->simds_seen;
-    simds[idx] |= (unsigned char)(1u << loc.simd);
-    if (!xcds[loc.xcd]) ++out->xcds_seen;
-    xcds[loc.xcd] = 1;
-    if (!r.fail_mask) continue;
-    ++out->waves_bad;
-    for (int t = 0; t < CRO_FMT_TESTS; ++t)
-      if (r.fail_mask & (1u << t)) ++out->bad[t];
-    if (!(simds[idx] & 0x80u)) {
-      simds[idx] |= 0x80u;
-      ++out->cus_bad;
-    }
-    if (out->first_bad_index < 0) {
-      out->first_bad_index = (long long)i;
-      out->xcd = (int)loc.xcd;
-      out->se = (int)loc.se;
-      out->sh = (int)loc.sh;
-      out->cu = (int)loc.cu;
-      out->simd = (int)loc.simd;
-      out->first_fail_mask = r.fail_mask;
-      out->n_bad = r.n_bad;
-      out->first_bad = r.first_bad;
-      out->bits_bad = r.bits_bad;
-    }
-  }
+  CroWaveSummary s;
+  cro_wave_summarize(records, n, &s);
+  cro_wave_common(s, out);
+  for (int t = 0; t < CRO_FMT_TESTS; ++t) out->bad[t] = s.bad[t];
 }
 
 // -- C ABI (libcroformats.so) -----------------------------------------------------

@@ -466,8 +466,7 @@ struct FmtCtx : CtxBase {
   uint32_t* dX = nullptr;
   uint32_t* dX2 = nullptr;  // selftest_also's
   uint32_t hE[CRO_FMT_TESTS][2 * CRO_FMT_MAX_ELEMS];
-  CroFormatsRecord* d_records = nullptr;
-  size_t records_cap = 0;
+  RecordBuf<CroFormatsRecord> records;
 };
 FmtCtx g_fctx[kMaxDevices];
 
@@ -534,17 +533,6 @@ int prepare(FmtCtx* ctx, int device, uint32_t seed, CroFormatsResult* out) {
   return 0;
 }
 
-// The record buffer holds at least n records afterwards.
-int reserve_records(FmtCtx* ctx, size_t n, CroFormatsResult* out) {
-  if (ctx->records_cap >= n) return 0;
-  if (ctx->d_records) (void)hipFree(ctx->d_records);
-  ctx->d_records = nullptr;
-  ctx->records_cap = 0;
-  CHECK(hipMalloc(&ctx->d_records, n * sizeof(CroFormatsRecord)));
-  ctx->records_cap = n;
-  return 0;
-}
-
 int run_formats(int device, const CroFormatsOpts* opts, CroFormatsResult* out,
                 CroFormatsRecord* records_out, int max_records) {
   CroFormatsOpts o;
@@ -585,8 +573,7 @@ int run_formats(int device, const CroFormatsOpts* opts, CroFormatsResult* out,
   const int grid = o.grid_blocks ? o.grid_blocks : ctx->cus;
   if (grid < 1) return bad_arg(out, "device reports no compute units");
   const size_t per_round = (size_t)grid * kWaves;
-  const size_t n_max = per_round * (size_t)max_rounds;
-  if (reserve_records(ctx, n_max, out) != 0) return -1;
+  CHECK(ctx->records.reserve(per_round * (size_t)max_rounds));
   out->cus_expected = ctx->cus;
   out->grid_blocks = grid;
   out->iters = iters;
@@ -621,43 +608,16 @@ int run_formats(int device, const CroFormatsOpts* opts, CroFormatsResult* out,
     if (o.selftest_also) CHECK(flipped(o.selftest_also - 1, o.selftest_elem + 1, ctx->dX2));
   }
 
-  std::vector<CroFormatsRecord> records(n_max);
-  CHECK(hipMemset(ctx->d_records, 0, n_max * sizeof(CroFormatsRecord)));
-  int rounds = 0;
-  double gpu_ms = 0.0;
-  for (;;) {
-    p.records = ctx->d_records + (size_t)rounds * per_round;
-    const auto one_round = [&] {
-      hipLaunchKernelGGL(formats_kernel, dim3(grid), dim3(kBlock),
-                         (size_t)CRO_COV_MAX_LDS_BYTES, 0, p);
-    };
-    float ms = 0.f;
-    CHECK(timed_ms(*ctx, &ms, one_round));
-    gpu_ms += ms;
-    CHECK(hipMemcpy(records.data() + (size_t)rounds * per_round, p.records,
-                     per_round * sizeof(CroFormatsRecord), hipMemcpyDeviceToHost));
-    ++rounds;
-    cro_formats_aggregate(records.data(), (size_t)rounds * per_round, &out->agg);
-    const bool covered =
-        out->agg.cus_seen >= ctx->cus && out->agg.simds_seen >= 4 * out->agg.cus_seen;
-    if (out->agg.waves_bad || covered || rounds >= max_rounds) break;
-  }
-  out->rounds = rounds;
-  out->gpu_ms = gpu_ms;
-  const size_t n = (size_t)rounds * per_round;
-  if (records_out && max_records > 0) {
-    const size_t m = n < (size_t)max_records ? n : (size_t)max_records;
-    memcpy(records_out, records.data(), m * sizeof(CroFormatsRecord));
-  }
-  const CroFormatsAgg& a = out->agg;
-  if (a.waves_run != n) {
-    // a wave that never wrote its record: the launch did not run to the end
-    snprintf(out->msg, sizeof(out->msg), "%llu of %zu waves reported", a.waves_run, n);
+  const auto launch = [&](CroFormatsRecord* d_round) {
+    p.records = d_round;
+    hipLaunchKernelGGL(formats_kernel, dim3(grid), dim3(kBlock), (size_t)CRO_COV_MAX_LDS_BYTES, 0,
+                       p);
+  };
+  if (run_rounds(*ctx, ctx->records.d, ctx->cus, per_round, max_rounds, launch,
+                 cro_formats_aggregate, out, records_out, max_records) != 0)
     return -1;
-  }
+  const CroFormatsAgg& a = out->agg;
   if (a.waves_bad) {
-    out->first_bad_round = (int)((size_t)a.first_bad_index / per_round);
-    out->first_bad_record = (int)((size_t)a.first_bad_index % per_round);
     snprintf(out->failed_test, sizeof(out->failed_test), "%s",
              cro_fmt_test_name(a.first_fail_mask));
     snprintf(out->msg, sizeof(out->msg),
@@ -667,23 +627,7 @@ int run_formats(int device, const CroFormatsOpts* opts, CroFormatsResult* out,
              a.waves_bad, a.waves_run, a.cus_bad);
     return -32;
   }
-  if (o.min_cu_fraction > 0.0 && (double)a.cus_seen < o.min_cu_fraction * (double)ctx->cus) {
-    snprintf(out->msg, sizeof(out->msg),
-             "coverage %d of %d CUs after %d rounds is below the floor %.3f", a.cus_seen,
-             ctx->cus, rounds, o.min_cu_fraction);
-    return -33;
-  }
-  out->ok = 1;
-  snprintf(out->msg, sizeof(out->msg), "ok");
-  return 0;
-}
-
-void clear_result(CroFormatsResult* out) {
-  memset(out, 0, sizeof(*out));
-  out->first_bad_round = out->first_bad_record = -1;
-  out->agg.first_bad_index = -1;
-  out->agg.xcd = out->agg.se = out->agg.sh = out->agg.cu = out->agg.simd = -1;
-  out->agg.first_bad = ~0u;
+  return coverage_floor(out, ctx->cus, o.min_cu_fraction, -33);
 }
 
 }  // namespace
@@ -691,7 +635,7 @@ void clear_result(CroFormatsResult* out) {
 extern "C" int cro_formats_run_records(int device, const struct CroFormatsOpts* opts,
                                        struct CroFormatsResult* out,
                                        struct CroFormatsRecord* records_out, int max_records) {
-  clear_result(out);
+  clear_result(out, cro_formats_aggregate);
   const double t0 = now_ms();
   out->rc = run_formats(device, opts, out, records_out, max_records);
   out->t_total_ms = now_ms() - t0;

@@ -415,8 +415,7 @@ __global__ __launch_bounds__(kBlock) void movement_kernel(MovParams p) {
 struct MovCtx : CtxBase {
   int cus = 0;
   unsigned char* d_src = nullptr;
-  CroMovementRecord* d_records = nullptr;
-  size_t records_cap = 0;
+  RecordBuf<CroMovementRecord> records;
 };
 MovCtx g_mctx[kMaxDevices];
 
@@ -437,17 +436,6 @@ int prepare(MovCtx* ctx, int device, CroMovementResult* out) {
   return 0;
 }
 
-// The record buffer holds at least n records afterwards.
-int reserve_records(MovCtx* ctx, size_t n, CroMovementResult* out) {
-  if (ctx->records_cap >= n) return 0;
-  if (ctx->d_records) (void)hipFree(ctx->d_records);
-  ctx->d_records = nullptr;
-  ctx->records_cap = 0;
-  CHECK(hipMalloc(&ctx->d_records, n * sizeof(CroMovementRecord)));
-  ctx->records_cap = n;
-  return 0;
-}
-
 int run_movement(int device, const CroMovementOpts* opts, CroMovementResult* out,
                  CroMovementRecord* records_out, int max_records) {
   CroMovementOpts o;
@@ -456,8 +444,9 @@ int run_movement(int device, const CroMovementOpts* opts, CroMovementResult* out
   if (o.grid_blocks < 0 || o.grid_blocks > kMaxGrid) return bad_arg(out, "grid_blocks");
   if (o.iters < 0 || o.iters > kMaxIters) return bad_arg(out, "iters");
   if (o.max_rounds < 0 || o.max_rounds > kMaxRounds) return bad_arg(out, "max_rounds");
-  // (a floor above 1 is allowed: no device can meet it, which is how the
-  // tests reach rc -37 on clean data)
+  // Unlike the compute and format stages, which stop at 1.0, this one allows
+  // a floor above 1: no device can meet it, which is how the tests reach rc
+  // -37 on clean data.
   if (!(o.min_cu_fraction >= 0.0 && o.min_cu_fraction <= 2.0))
     return bad_arg(out, "min_cu_fraction");
   const int iters = o.iters ? o.iters : kDefaultIters;
@@ -490,8 +479,7 @@ int run_movement(int device, const CroMovementOpts* opts, CroMovementResult* out
   const int grid = o.grid_blocks ? o.grid_blocks : ctx->cus;
   if (grid < 1) return bad_arg(out, "device reports no compute units");
   const size_t per_round = (size_t)grid * kWaves;
-  const size_t n_max = per_round * (size_t)max_rounds;
-  if (reserve_records(ctx, n_max, out) != 0) return -1;
+  CHECK(ctx->records.reserve(per_round * (size_t)max_rounds));
   out->cus_expected = ctx->cus;
   out->grid_blocks = grid;
   out->iters = iters;
@@ -508,43 +496,16 @@ int run_movement(int device, const CroMovementOpts* opts, CroMovementResult* out
   p.inj_key = o.selftest_key;
   p.inj_flip = 1u << (o.selftest_bit & 31);
 
-  std::vector<CroMovementRecord> records(n_max);
-  CHECK(hipMemset(ctx->d_records, 0, n_max * sizeof(CroMovementRecord)));
-  int rounds = 0;
-  double gpu_ms = 0.0;
-  for (;;) {
-    p.records = ctx->d_records + (size_t)rounds * per_round;
-    const auto one_round = [&] {
-      hipLaunchKernelGGL(movement_kernel, dim3(grid), dim3(kBlock),
-                         (size_t)CRO_COV_MAX_LDS_BYTES, 0, p);
-    };
-    float ms = 0.f;
-    CHECK(timed_ms(*ctx, &ms, one_round));
-    gpu_ms += ms;
-    CHECK(hipMemcpy(records.data() + (size_t)rounds * per_round, p.records,
-                     per_round * sizeof(CroMovementRecord), hipMemcpyDeviceToHost));
-    ++rounds;
-    cro_movement_aggregate(records.data(), (size_t)rounds * per_round, &out->agg);
-    const bool covered =
-        out->agg.cus_seen >= ctx->cus && out->agg.simds_seen >= 4 * out->agg.cus_seen;
-    if (out->agg.waves_bad || covered || rounds >= max_rounds) break;
-  }
-  out->rounds = rounds;
-  out->gpu_ms = gpu_ms;
-  const size_t n = (size_t)rounds * per_round;
-  if (records_out && max_records > 0) {
-    const size_t m = n < (size_t)max_records ? n : (size_t)max_records;
-    memcpy(records_out, records.data(), m * sizeof(CroMovementRecord));
-  }
-  const CroMovementAgg& a = out->agg;
-  if (a.waves_run != n) {
-    // a wave that never wrote its record: the launch did not run to the end
-    snprintf(out->msg, sizeof(out->msg), "%llu of %zu waves reported", a.waves_run, n);
+  const auto launch = [&](CroMovementRecord* d_round) {
+    p.records = d_round;
+    hipLaunchKernelGGL(movement_kernel, dim3(grid), dim3(kBlock), (size_t)CRO_COV_MAX_LDS_BYTES,
+                       0, p);
+  };
+  if (run_rounds(*ctx, ctx->records.d, ctx->cus, per_round, max_rounds, launch,
+                 cro_movement_aggregate, out, records_out, max_records) != 0)
     return -1;
-  }
+  const CroMovementAgg& a = out->agg;
   if (a.waves_bad) {
-    out->first_bad_round = (int)((size_t)a.first_bad_index / per_round);
-    out->first_bad_record = (int)((size_t)a.first_bad_index % per_round);
     snprintf(out->failed_test, sizeof(out->failed_test), "%s",
              cro_mov_test_name(a.first_fail_mask));
     snprintf(out->msg, sizeof(out->msg),
@@ -555,15 +516,7 @@ int run_movement(int device, const CroMovementOpts* opts, CroMovementResult* out
              a.cus_bad);
     return -36;
   }
-  if (o.min_cu_fraction > 0.0 && (double)a.cus_seen < o.min_cu_fraction * (double)ctx->cus) {
-    snprintf(out->msg, sizeof(out->msg),
-             "coverage %d of %d CUs after %d rounds is below the floor %.3f", a.cus_seen,
-             ctx->cus, rounds, o.min_cu_fraction);
-    return -37;
-  }
-  out->ok = 1;
-  snprintf(out->msg, sizeof(out->msg), "ok");
-  return 0;
+  return coverage_floor(out, ctx->cus, o.min_cu_fraction, -37);
 }
 
 template <int T>
@@ -576,9 +529,7 @@ void launch_tile(const TileArgs& t) {
 extern "C" int cro_movement_run_records(int device, const struct CroMovementOpts* opts,
                                         struct CroMovementResult* out,
                                         struct CroMovementRecord* records_out, int max_records) {
-  memset(out, 0, sizeof(*out));
-  out->first_bad_round = out->first_bad_record = -1;
-  cro_movement_agg_clear(&out->agg);
+  clear_result(out, cro_movement_aggregate);
   const double t0 = now_ms();
   out->rc = run_movement(device, opts, out, records_out, max_records);
   out->t_total_ms = now_ms() - t0;

@@ -17,7 +17,8 @@ import ctypes
 import os
 from typing import Optional
 
-from .probe import _gpu_present, _lcg_stream, _result_dict, decode_location
+from .probe import (_gpu_present, _lcg_stream, _result_dict, _run_with_records,
+                    aggregate_wave_records)
 
 _LIB_PATH = os.path.join(os.path.dirname(__file__), "..", "hip", "libcroformats.so")
 
@@ -208,23 +209,11 @@ def run_formats(device: int = 0, **opts) -> dict:
 def run_formats_records(device: int = 0, **opts):
     """As run_formats, and returns the raw per-wave records as well: a
     structured numpy array of rounds * grid_blocks * 4 records, round-major."""
-    import numpy as np
-
     lib = load_formats_library(required=True)
     c_opts = _formats_opts(**opts)
     res = CroFormatsResult()
-    # room for what was asked; a default grid is one workgroup per CU, and
-    # no device of this family has more than 1024 of them
-    blocks = c_opts.grid_blocks or 1024
-    rounds = c_opts.max_rounds or 4
-    cap = max(blocks * 4 * rounds, 1)
-    buf = (CroFormatsRecord * cap)()
-    rc = lib.cro_formats_run_records(device, ctypes.byref(c_opts), ctypes.byref(res), buf, cap)
-    out = _result_dict(res, rc)
-    n = min(out["rounds"] * out["grid_blocks"] * 4, cap)
-    dtype = np.dtype([(name, np.uint32) for name, _ in CroFormatsRecord._fields_])
-    records = np.frombuffer(buf, dtype=dtype, count=cap)[:n].copy()
-    return out, records
+    return _run_with_records(CroFormatsRecord, c_opts, res, lambda buf, cap: (
+        lib.cro_formats_run_records(device, ctypes.byref(c_opts), ctypes.byref(res), buf, cap)))
 
 
 # -- numpy mirrors of croformats.h ---------------------------------------------------
@@ -393,41 +382,8 @@ def formats_abs_quanta(test, seed: int = 0) -> float:
 
 
 def aggregate_formats_records(records) -> dict:
-    """numpy mirror of cro_formats_aggregate over a structured record array
-    (or any mapping of equal-length uint32 arrays)."""
-    import numpy as np
-
-    valid = np.asarray(records["valid"]) != 0
-    xcc = np.asarray(records["xcc_id"])[valid].astype(np.int64)
-    hw = np.asarray(records["hw_id"])[valid].astype(np.int64)
-    mask = np.asarray(records["fail_mask"])[valid].astype(np.int64)
-    keys = ((xcc & 0xF) << 16) | (hw & 0xFF00)
-    simd = (hw >> 4) & 0x3
-    bad = mask != 0
-    out = {"waves_run": int(valid.sum()), "waves_bad": int(bad.sum())}
-    for bit, name in enumerate(FORMATS_TESTS):
-        out[f"bad_{name}"] = int(((mask >> bit) & 1).sum())
-    out.update({
-        "first_bad_index": -1,
-        "cus_seen": int(np.unique(keys).size),
-        "xcds_seen": int(np.unique(xcc & 0xF).size),
-        "simds_seen": int(np.unique(keys * 4 + simd).size),
-        "cus_bad": int(np.unique(keys[bad]).size),
-        "xcd": -1, "se": -1, "sh": -1, "cu": -1, "simd": -1,
-        "first_fail_mask": 0, "n_bad": 0, "first_bad": 0xFFFFFFFF, "bits_bad": 0,
-    })
-    if bad.any():
-        first = int(np.flatnonzero(valid)[np.flatnonzero(bad)[0]])
-        loc = decode_location(int(records["xcc_id"][first]), int(records["hw_id"][first]))
-        out.update({k: int(loc[k]) for k in ("xcd", "se", "sh", "cu", "simd")})
-        out.update(
-            first_bad_index=first,
-            first_fail_mask=int(records["fail_mask"][first]),
-            n_bad=int(records["n_bad"][first]),
-            first_bad=int(records["first_bad"][first]),
-            bits_bad=int(records["bits_bad"][first]),
-        )
-    return out
+    """numpy mirror of cro_formats_aggregate (probe.aggregate_wave_records)."""
+    return aggregate_wave_records(records, FORMATS_TESTS)[0]
 
 
 def formats_test_name(fail_mask: int) -> str:

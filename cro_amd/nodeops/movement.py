@@ -18,7 +18,7 @@ import ctypes
 import os
 from typing import Optional
 
-from .probe import _gpu_present, _result_dict, decode_location
+from .probe import _gpu_present, _result_dict, _run_with_records, aggregate_wave_records
 
 _LIB_PATH = os.path.join(os.path.dirname(__file__), "..", "hip", "libcromovement.so")
 
@@ -230,23 +230,11 @@ def run_movement(device: int = 0, **opts) -> dict:
 def run_movement_records(device: int = 0, **opts):
     """As run_movement, and returns the raw per-wave records as well: a
     structured numpy array of rounds * grid_blocks * 4 records, round-major."""
-    import numpy as np
-
     lib = load_movement_library(required=True)
     c_opts = _movement_opts(**opts)
     res = CroMovementResult()
-    # room for what was asked; a default grid is one workgroup per CU, and
-    # no device of this family has more than 1024 of them
-    blocks = c_opts.grid_blocks or 1024
-    rounds = c_opts.max_rounds or 4
-    cap = max(blocks * 4 * rounds, 1)
-    buf = (CroMovementRecord * cap)()
-    rc = lib.cro_movement_run_records(device, ctypes.byref(c_opts), ctypes.byref(res), buf, cap)
-    out = _result_dict(res, rc)
-    n = min(out["rounds"] * out["grid_blocks"] * 4, cap)
-    dtype = np.dtype([(name, np.uint32) for name, _ in CroMovementRecord._fields_])
-    records = np.frombuffer(buf, dtype=dtype, count=cap)[:n].copy()
-    return out, records
+    return _run_with_records(CroMovementRecord, c_opts, res, lambda buf, cap: (
+        lib.cro_movement_run_records(device, ctypes.byref(c_opts), ctypes.byref(res), buf, cap)))
 
 
 def movement_tile(device: int, test, variant: int, data, addr=None):
@@ -632,41 +620,10 @@ def movement_expected(test, variant: int, seed: int = 0, rep: int = 0, wave: int
 
 
 def aggregate_movement_records(records) -> dict:
-    """numpy mirror of cro_movement_aggregate over a structured record array
-    (or any mapping of equal-length uint32 arrays)."""
-    import numpy as np
-
-    valid = np.asarray(records["valid"]) != 0
-    xcc = np.asarray(records["xcc_id"])[valid].astype(np.int64)
-    hw = np.asarray(records["hw_id"])[valid].astype(np.int64)
-    mask = np.asarray(records["fail_mask"])[valid].astype(np.int64)
-    keys = ((xcc & 0xF) << 16) | (hw & 0xFF00)
-    simd = (hw >> 4) & 0x3
-    bad = mask != 0
-    out = {"waves_run": int(valid.sum()), "waves_bad": int(bad.sum())}
-    for bit, name in enumerate(MOVEMENT_TESTS):
-        out[f"bad_{name}"] = int(((mask >> bit) & 1).sum())
-    out.update({
-        "cus_seen": int(np.unique(keys).size),
-        "xcds_seen": int(np.unique(xcc & 0xF).size),
-        "simds_seen": int(np.unique(keys * 4 + simd).size),
-        "cus_bad": int(np.unique(keys[bad]).size),
-        "xcd": -1, "se": -1, "sh": -1, "cu": -1, "simd": -1,
-        "fail_mask": int(np.bitwise_or.reduce(mask)) if mask.size else 0,
-        "first_fail_mask": 0, "n_bad": 0, "first_bad": 0xFFFFFFFF, "bits_bad": 0,
-        "first_bad_index": -1,
-    })
-    if bad.any():
-        first = int(np.flatnonzero(valid)[np.flatnonzero(bad)[0]])
-        loc = decode_location(int(records["xcc_id"][first]), int(records["hw_id"][first]))
-        out.update({k: int(loc[k]) for k in ("xcd", "se", "sh", "cu", "simd")})
-        out.update(
-            first_bad_index=first,
-            first_fail_mask=int(records["fail_mask"][first]),
-            n_bad=int(records["n_bad"][first]),
-            first_bad=int(records["first_bad"][first]),
-            bits_bad=int(records["bits_bad"][first]),
-        )
+    """numpy mirror of cro_movement_aggregate: probe.aggregate_wave_records
+    and the OR of the fail masks."""
+    out, fail_mask, _ = aggregate_wave_records(records, MOVEMENT_TESTS)
+    out["fail_mask"] = fail_mask
     return out
 
 

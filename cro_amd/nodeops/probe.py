@@ -682,33 +682,40 @@ def run_compute(device: int = 0, **opts) -> dict:
     return _result_dict(res, rc)
 
 
+def _run_with_records(record_type, c_opts, res, call):
+    """What the per-wave stages' run_*_records share: a buffer of
+    ``record_type`` sized for the options, ``call(buf, cap)`` (the library's
+    *_records entry; returns its rc), and the records it returned as a
+    structured numpy array next to the result dict."""
+    import numpy as np
+
+    # room for what was asked; a default grid is one workgroup per CU, and
+    # no device of this family has more than 1024 of them
+    blocks = c_opts.grid_blocks or 1024
+    rounds = c_opts.max_rounds or 4
+    cap = max(blocks * 4 * rounds, 1)
+    buf = (record_type * cap)()
+    out = _result_dict(res, call(buf, cap))
+    n = min(out["rounds"] * out["grid_blocks"] * 4, cap)
+    dtype = np.dtype([(name, np.uint32) for name, _ in record_type._fields_])
+    return out, np.frombuffer(buf, dtype=dtype, count=cap)[:n].copy()
+
+
 def run_compute_records(device: int = 0, tiles=None, **opts):
     """As run_compute, and returns the raw per-wave records as well: a
     structured numpy array of rounds * grid_blocks * 4 records, round-major.
     ``tiles`` (for tests): a dict with any of ``"f32"`` (256 float32), ``"i8"``
     (256 int32) and ``"bf16"`` (1024 float32), each taking the place of that
     test's expected tile in this call only."""
-    import numpy as np
-
     lib = load_library(required=True)
     c_opts = _compute_opts(**opts)
     c_tiles = _caller_tiles(tiles)
     res = CroComputeResult()
-    # room for what was asked; a default grid is one workgroup per CU, and
-    # no device of this family has more than 1024 of them
-    blocks = c_opts.grid_blocks or 1024
-    rounds = c_opts.max_rounds or 4
-    cap = max(blocks * 4 * rounds, 1)
-    buf = (CroCoverageRecord * cap)()
-    rc = lib.cro_probe_compute_tiles(
-        device, ctypes.byref(c_opts), *[t.ctypes.data if t is not None else None for t in c_tiles],
-        ctypes.byref(res), buf, cap,
-    )
-    out = _result_dict(res, rc)
-    n = min(out["rounds"] * out["grid_blocks"] * 4, cap)
-    dtype = np.dtype([(name, np.uint32) for name, _ in CroCoverageRecord._fields_])
-    records = np.frombuffer(buf, dtype=dtype, count=cap)[:n].copy()
-    return out, records
+    return _run_with_records(CroCoverageRecord, c_opts, res, lambda buf, cap: (
+        lib.cro_probe_compute_tiles(
+            device, ctypes.byref(c_opts),
+            *[t.ctypes.data if t is not None else None for t in c_tiles],
+            ctypes.byref(res), buf, cap)))
 
 
 def compute_lds_dump(device: int, grid_blocks: int, lds_bytes: int, seed: int = 0, invert=0,
@@ -878,9 +885,13 @@ def decode_cu_key(key) -> dict:
     return {k: loc[k] for k in ("xcd", "se", "sh", "cu")}
 
 
-def aggregate_records(records) -> dict:
-    """numpy mirror of cro_coverage_aggregate over a structured record array
-    (or any mapping of equal-length uint32 arrays)."""
+def aggregate_wave_records(records, tests):
+    """numpy mirror of cro_wave_summarize (crocoverage.h) over a structured
+    record array (or any mapping of equal-length uint32 arrays) of a stage
+    whose fail-mask bits are ``tests``.  Returns what every stage's aggregate
+    holds, with the per-test counts as ``bad_<test>``, and apart from it what
+    only some hold: the OR of the fail masks and the keys of the CUs with a bad
+    wave, in order of first appearance."""
     import numpy as np
 
     valid = np.asarray(records["valid"]) != 0
@@ -890,17 +901,11 @@ def aggregate_records(records) -> dict:
     keys = cu_key(xcc, hw)
     simd = (hw >> 4) & 0x3
     bad = mask != 0
-    bad_keys = []
-    for key in keys[bad]:
-        if int(key) not in bad_keys:
-            bad_keys.append(int(key))
-    out = {
-        "waves_run": int(valid.sum()),
-        "waves_bad": int(bad.sum()),
-        "bad_f32": int(((mask & 1) != 0).sum()),
-        "bad_i8": int(((mask & 2) != 0).sum()),
-        "bad_bf16": int(((mask & 4) != 0).sum()),
-        "bad_lds": int(((mask & 8) != 0).sum()),
+    bad_keys = list(dict.fromkeys(keys[bad].tolist()))
+    out = {"waves_run": int(valid.sum()), "waves_bad": int(bad.sum())}
+    for bit, name in enumerate(tests):
+        out[f"bad_{name}"] = int(((mask >> bit) & 1).sum())
+    out.update({
         "first_bad_index": -1,
         "cus_seen": int(np.unique(keys).size),
         "xcds_seen": int(np.unique(xcc & 0xF).size),
@@ -908,9 +913,7 @@ def aggregate_records(records) -> dict:
         "cus_bad": len(bad_keys),
         "xcd": -1, "se": -1, "sh": -1, "cu": -1, "simd": -1,
         "first_fail_mask": 0, "n_bad": 0, "first_bad": 0xFFFFFFFF, "bits_bad": 0,
-        "n_bad_cu_keys": min(len(bad_keys), 8),
-        "bad_cu_keys": bad_keys[:8],
-    }
+    })
     if bad.any():
         first = int(np.flatnonzero(valid)[np.flatnonzero(bad)[0]])
         loc = decode_location(int(records["xcc_id"][first]), int(records["hw_id"][first]))
@@ -922,6 +925,14 @@ def aggregate_records(records) -> dict:
             first_bad=int(records["first_bad"][first]),
             bits_bad=int(records["bits_bad"][first]),
         )
+    return out, int(np.bitwise_or.reduce(mask)) if mask.size else 0, bad_keys
+
+
+def aggregate_records(records) -> dict:
+    """numpy mirror of cro_coverage_aggregate: aggregate_wave_records and the
+    first eight bad CU keys."""
+    out, _, bad_keys = aggregate_wave_records(records, ("f32", "i8", "bf16", "lds"))
+    out.update(n_bad_cu_keys=min(len(bad_keys), 8), bad_cu_keys=bad_keys[:8])
     return out
 
 
