@@ -22,6 +22,9 @@
 //       [--movement [--movement-min-cu-fraction X]]  + the data-movement stage:
 //                                            cross-lane, transposed LDS reads, LDS-DMA
 //                                            (libcromovement.so, loaded at run time)
+//       [--alu [--alu-min-cu-fraction X]]    + the ALU stage: vector and scalar ALUs,
+//                                            transcendental consensus
+//                                            (libcroalu.so, loaded at run time)
 //                                            + exact checks on every CU and SIMD
 //   croagent scrub  [--device N | --bdf B]   overwrite and verify VRAM before drain
 //       [--max-mib N] [--reserve-mib N] [--min-fraction X]
@@ -46,6 +49,7 @@
 #include "../hip/croformats.h"
 #include "../hip/crocoherence.h"
 #include "../hip/cromovement.h"
+#include "../hip/croalu.h"
 #include "../hip/croregscrub.h"
 #include "../hip/croscrub.h"
 
@@ -404,20 +408,41 @@ void print_movement(const CroMovementResult& r) {
          r.failed_test, r.msg);
 }
 
+// The ALU stage's result, keys as nodeops/alu.py run_alu.
+void print_alu(const CroAluResult& r) {
+  const CroAluAgg& a = r.agg;
+  printf("\"alu\":{\"ok\":%s,\"rc\":%d,\"cus_expected\":%d,\"rounds\":%d,"
+         "\"waves_run\":%llu,\"waves_bad\":%llu,",
+         r.ok ? "true" : "false", r.rc, r.cus_expected, r.rounds, a.waves_run, a.waves_bad);
+  for (int t = 0; t < CRO_ALU_TESTS; ++t) printf("\"bad_%s\":%llu,", kCroAluTestNames[t], a.bad[t]);
+  printf("\"cus_seen\":%d,\"xcds_seen\":%d,\"simds_seen\":%d,\"cus_bad\":%d,\"xcd\":%d,"
+         "\"se\":%d,\"sh\":%d,\"cu\":%d,\"simd\":%d,\"fail_mask\":%u,\"first_fail_mask\":%u,"
+         "\"n_bad\":%u,\"first_bad\":%u,\"bits_bad\":%u,\"first_bad_index\":%lld,"
+         "\"digest\":%u,\"no_majority\":%u,\"digest_waves\":%llu,",
+         a.cus_seen, a.xcds_seen, a.simds_seen, a.cus_bad, a.xcd, a.se, a.sh, a.cu, a.simd,
+         a.fail_mask, a.first_fail_mask, a.n_bad, a.first_bad, a.bits_bad, a.first_bad_index,
+         a.digest, a.no_majority, a.digest_waves);
+  printf("\"first_bad_round\":%d,\"first_bad_record\":%d,\"grid_blocks\":%d,\"iters\":%d,"
+         "\"gpu_ms\":%.3f,\"t_total_ms\":%.3f,\"failed_test\":\"%s\",\"msg\":\"%s\"}",
+         r.first_bad_round, r.first_bad_record, r.grid_blocks, r.iters, r.gpu_ms, r.t_total_ms,
+         r.failed_test, r.msg);
+}
+
 int scrub_unavailable(const std::string& msg);
 void* load_entry(const char* soname, const char* symbol, std::string* why);
 
 // The quick probe first, then with --compute the compute-coverage stage, then
 // with --formats the matrix-format stage, then with --coherence the coherence
-// stage, then with --movement the data-movement stage, then with --deep the
-// data-integrity stage; a device that failed a
+// stage, then with --movement the data-movement stage, then with --alu the
+// ALU stage, then with --deep the data-integrity stage; a device that failed a
 // stage is not stressed further.  Top-level "ok" and "msg" cover all stages
 // run.  The formats and coherence libraries are looked up before anything runs: a probe that was asked for the stage and cannot run it says
 // so, in the scrubs' shape, and probes nothing.
 int cmd_probe_staged(int device, bool compute, const CroComputeOpts& copts, bool deep,
                      const CroIntegrityOpts& opts, const CroFormatsOpts* fopts = nullptr,
                      const CroCoherenceOpts* hopts = nullptr,
-                     const CroMovementOpts* mopts = nullptr) {
+                     const CroMovementOpts* mopts = nullptr,
+                     const CroAluOpts* aopts = nullptr) {
   typedef int (*FormatsRun)(int, const CroFormatsOpts*, CroFormatsResult*);
   FormatsRun run_formats = nullptr;
   if (fopts) {
@@ -439,14 +464,23 @@ int cmd_probe_staged(int device, bool compute, const CroComputeOpts& copts, bool
     run_movement = (MovementRun)load_entry("libcromovement.so", "cro_movement_run", &why);
     if (run_movement == nullptr) return scrub_unavailable(why);
   }
+  typedef int (*AluRun)(int, const CroAluOpts*, CroAluResult*);
+  AluRun run_alu = nullptr;
+  if (aopts) {
+    std::string why;
+    run_alu = (AluRun)load_entry("libcroalu.so", "cro_alu_run", &why);
+    if (run_alu == nullptr) return scrub_unavailable(why);
+  }
   CroProbeResult result;
   int rc = cro_probe_run(device, &result);
   CroComputeResult comp;
   CroFormatsResult fmts;
   CroCoherenceResult coh;
   CroMovementResult mov;
+  CroAluResult alu;
   CroIntegrityResult integ;
-  bool ran_comp = false, ran_fmts = false, ran_coh = false, ran_mov = false, ran = false;
+  bool ran_comp = false, ran_fmts = false, ran_coh = false, ran_mov = false, ran_alu = false;
+  bool ran = false;
   bool ok = result.ok;
   const char* msg = result.msg;
   if (ok && compute) {
@@ -481,6 +515,14 @@ int cmd_probe_staged(int device, bool compute, const CroComputeOpts& copts, bool
       msg = mov.msg;
     }
   }
+  if (ok && run_alu) {
+    run_alu(device, aopts, &alu);
+    ran_alu = true;
+    if (!alu.ok) {
+      ok = false;
+      msg = alu.msg;
+    }
+  }
   if (ok && deep) {
     cro_probe_integrity(device, &opts, &integ);
     ran = true;
@@ -510,6 +552,10 @@ int cmd_probe_staged(int device, bool compute, const CroComputeOpts& copts, bool
   if (ran_mov) {
     printf(",");
     print_movement(mov);
+  }
+  if (ran_alu) {
+    printf(",");
+    print_alu(alu);
   }
   if (ran) {
     printf(",");
@@ -700,6 +746,9 @@ int main(int argc, char** argv) {
   bool movement = false;
   CroMovementOpts movement_opts;  // nor here
   memset(&movement_opts, 0, sizeof(movement_opts));
+  bool alu = false;
+  CroAluOpts alu_opts;  // nor here
+  memset(&alu_opts, 0, sizeof(alu_opts));
   for (int i = 2; i < argc; ++i) {
     std::string arg = argv[i];
     if (arg == "--sysroot" && i + 1 < argc) g_sysroot = argv[++i];
@@ -715,6 +764,8 @@ int main(int argc, char** argv) {
     else if (arg == "--coherence-min-cu-fraction" && i + 1 < argc) coherence_opts.min_cu_fraction = atof(argv[++i]);
     else if (arg == "--movement") movement = true;
     else if (arg == "--movement-min-cu-fraction" && i + 1 < argc) movement_opts.min_cu_fraction = atof(argv[++i]);
+    else if (arg == "--alu") alu = true;
+    else if (arg == "--alu-min-cu-fraction" && i + 1 < argc) alu_opts.min_cu_fraction = atof(argv[++i]);
     else if (arg == "--vram-mib" && i + 1 < argc) integ_opts.vram_bytes = atoll(argv[++i]) << 20;
     else if (arg == "--link-mib" && i + 1 < argc) integ_opts.link_bytes = atoll(argv[++i]) << 20;
     else if (arg == "--link-floor-gbps" && i + 1 < argc) integ_opts.link_floor_gbps = atof(argv[++i]);
@@ -742,7 +793,7 @@ int main(int argc, char** argv) {
     return cmd_probe_staged(device, compute, compute_opts, deep, integ_opts,
                             formats ? &formats_opts : nullptr,
                             coherence ? &coherence_opts : nullptr,
-                            movement ? &movement_opts : nullptr);
+                            movement ? &movement_opts : nullptr, alu ? &alu_opts : nullptr);
   }
   if (cmd == "scrub") {
     if (!bdf.empty()) {

@@ -109,6 +109,18 @@ def add_probe_arguments(p: argparse.ArgumentParser) -> None:
                    help="movement probe: fail when fewer than this fraction of "
                    "the device's CUs were reached (0 = off: coverage is "
                    "reported, only data gates)")
+    p.add_argument("--probe-alu", choices=["off", "on"],
+                   default=env("CRO_PROBE_ALU", "off"),
+                   help="on: additionally run exact checks of the vector ALU (integer, bit, "
+                   "packed, dot, f32, f16, f64, conversions, compares) and the scalar ALU "
+                   "and a consensus check of the transcendental unit on every CU and SIMD, "
+                   "at either level; a failure names the check, form, row and lane and the "
+                   "XCD, CU and SIMD")
+    p.add_argument("--probe-alu-min-cu-fraction", type=float,
+                   default=float(env("CRO_PROBE_ALU_MIN_CU_FRACTION", "0")),
+                   help="alu probe: fail when fewer than this fraction of "
+                   "the device's CUs were reached (0 = off: coverage is "
+                   "reported, only data gates)")
 
 
 def select_probe_fn(args):
@@ -126,6 +138,8 @@ def select_probe_fn(args):
     if getattr(args, "probe_movement", "off") == "on":
         stages.update(movement=True,
                       movement_min_cu_fraction=args.probe_movement_min_cu_fraction)
+    if getattr(args, "probe_alu", "off") == "on":
+        stages.update(alu=True, alu_min_cu_fraction=args.probe_alu_min_cu_fraction)
     return make_probe_fn(
         args.probe_level,
         vram_bytes=args.probe_vram_mib << 20,
@@ -139,7 +153,7 @@ def select_probe_fn(args):
 
 def drop_unavailable_probe_stages(args, log) -> bool:
     """An optional probe stage with a library of its own (--probe-formats,
-    --probe-coherence, --probe-movement) that is on but whose library is not
+    --probe-coherence, --probe-movement, --probe-alu) that is on but whose library is not
     on this node: warn, switch the stage off in ``args`` and go on without it.
     True when one was switched off."""
     dropped = False
@@ -184,6 +198,20 @@ def drop_unavailable_probe_stages(args, log) -> bool:
         else:
             log.warning("gfx950 data-movement probe library unavailable; movement stage disabled")
             args.probe_movement = "off"
+            dropped = True
+    if getattr(args, "probe_alu", "off") == "on":
+        lib = None
+        try:
+            from ..nodeops.alu import load_alu_library
+
+            lib = load_alu_library(required=False)
+        except Exception:
+            pass
+        if lib is not None:
+            log.info("health probe ALU stage: on")
+        else:
+            log.warning("gfx950 ALU probe library unavailable; alu stage disabled")
+            args.probe_alu = "off"
             dropped = True
     return dropped
 

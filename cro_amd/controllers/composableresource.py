@@ -538,6 +538,26 @@ class ComposableResourceReconciler(Reconciler):
                     f"bits_bad=0x{int(movement.get('bits_bad', 0)):08x} "
                     f"cus_bad={movement.get('cus_bad')}: {probe}"
                 )
+            alu = probe.get("alu")
+            if isinstance(alu, dict) and not alu.get("ok", True):
+                # ALU stage: the check, which form, row and lane gave the
+                # wrong word, then where on the chip
+                from ..nodeops.alu import describe_first_bad as describe_alu
+
+                test = alu.get("failed_test") or (
+                    "coverage" if alu.get("rc") == -39 else "unknown"
+                )
+                self.metrics.probe_alu_failures_total.labels(test=test).inc()
+                what = ""
+                if alu.get("failed_test"):
+                    what = describe_alu(int(alu.get("first_bad", 0))) + " "
+                raise FabricError(
+                    f"gfx950 health probe failed: alu stage {test} {what}"
+                    f"xcd={alu.get('xcd')} se={alu.get('se')} "
+                    f"cu={alu.get('cu')} simd={alu.get('simd')} "
+                    f"bits_bad=0x{int(alu.get('bits_bad', 0)):08x} "
+                    f"cus_bad={alu.get('cus_bad')}: {probe}"
+                )
             integrity = probe.get("integrity")
             if isinstance(integrity, dict) and not integrity.get("ok", True):
                 # deep level: lead with what an operator needs to act on —
@@ -590,6 +610,14 @@ class ComposableResourceReconciler(Reconciler):
                     f"/{movement.get('cus_expected', 0)} CUs,"
                     f" {movement.get('simds_seen', 0)} SIMDs,"
                     f" {movement.get('gpu_ms', 0):.1f} ms"
+                )
+            alu = probe.get("alu")
+            if isinstance(alu, dict):
+                probe_note += (
+                    f"; alu: {alu.get('cus_seen', 0)}"
+                    f"/{alu.get('cus_expected', 0)} CUs,"
+                    f" {alu.get('simds_seen', 0)} SIMDs,"
+                    f" {alu.get('gpu_ms', 0):.1f} ms"
                 )
             integrity = probe.get("integrity")
             if isinstance(integrity, dict):

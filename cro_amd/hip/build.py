@@ -90,6 +90,16 @@ MOVEMENT_HEADERS = [
     COVERAGE_HEADER,  # for cro_cov_cu_key and cro_cov_decode
 ]
 MOVEMENT_OUT = os.path.join(HIP_DIR, "libcromovement.so")
+# ALU probe stage (vector and scalar ALUs, transcendental consensus): a
+# library of its own as well; croformats.h for the narrow formats' code tables
+ALU_SRC = os.path.join(HIP_DIR, "alu.hip")
+ALU_HEADERS = [
+    os.path.join(HIP_DIR, "croalu.h"),
+    os.path.join(HIP_DIR, "crohost.h"),
+    os.path.join(HIP_DIR, "croformats.h"),
+    COVERAGE_HEADER,  # for cro_cov_cu_key, cro_cov_decode and the aggregation core
+]
+ALU_OUT = os.path.join(HIP_DIR, "libcroalu.so")
 AGENT_SRC = os.path.join(AGENT_DIR, "croagent.cpp")
 AGENT_OUT = os.path.join(AGENT_DIR, "croagent")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -176,6 +186,16 @@ def build_movement(force: bool = False) -> str:
     return MOVEMENT_OUT
 
 
+def build_alu(force: bool = False) -> str:
+    """libcroalu.so: the ALU probe stage (alu.hip)."""
+    if force or _stale(ALU_OUT, [ALU_SRC] + ALU_HEADERS):
+        subprocess.run(
+            [HIPCC, *DEVICE_FLAGS, "-fPIC", "-shared", ALU_SRC, "-o", ALU_OUT],
+            check=True,
+        )
+    return ALU_OUT
+
+
 def build_agent(force: bool = False) -> str:
     """croagent: the native node-agent CLI (links libcroprobe; loads
     libcroscrub.so, libcroldsscrub.so, libcroregscrub.so, libcroformats.so and
@@ -214,4 +234,5 @@ if __name__ == "__main__":
     print(build_formats(force="--force" in sys.argv))
     print(build_coherence(force="--force" in sys.argv))
     print(build_movement(force="--force" in sys.argv))
+    print(build_alu(force="--force" in sys.argv))
     print(build_reg_scrub(force="--force" in sys.argv))

@@ -104,6 +104,14 @@ class Metrics:
             "optional CU-coverage floor)",
             ["test"],
         )
+        self.probe_alu_failures_total = Counter(
+            "cro_probe_alu_failures_total",
+            "Attaches refused by the probe's ALU stage, by the check that failed "
+            "(int_arith, bit_ops, pk_int, dot, f32, f16, f64, convert, "
+            "scale_convert, compare_select, salu, transcendental; coverage for "
+            "the optional CU-coverage floor)",
+            ["test"],
+        )
         self.scrub_failures_total = Counter(
             "cro_scrub_failures_total",
             "Scrubs before drain that did not pass, by reason (residue: words "
@@ -140,6 +148,7 @@ class Metrics:
                 cls._singleton.probe_formats_failures_total,
                 cls._singleton.probe_coherence_failures_total,
                 cls._singleton.probe_movement_failures_total,
+                cls._singleton.probe_alu_failures_total,
                 cls._singleton.scrub_failures_total,
                 cls._singleton.scrub_seconds,
                 cls._singleton.scrub_bytes_total,

@@ -941,7 +941,8 @@ def make_probe_fn(level: str = "quick", vram_bytes: int = 0, link_bytes: int = 0
                   compute_min_cu_fraction: float = 0.0, formats: bool = False,
                   formats_min_cu_fraction: float = 0.0, coherence: bool = False,
                   coherence_min_cu_fraction: float = 0.0, movement: bool = False,
-                  movement_min_cu_fraction: float = 0.0):
+                  movement_min_cu_fraction: float = 0.0, alu: bool = False,
+                  alu_min_cu_fraction: float = 0.0):
     """AmdNodeOps probe hook for a probe level.
 
     ``quick`` is the rate/matrix-pipe gate.  ``deep`` runs it first and, only
@@ -965,12 +966,17 @@ def make_probe_fn(level: str = "quick", vram_bytes: int = 0, link_bytes: int = 0
     ``movement=True`` adds the data-movement stage (nodeops/movement.py: the
     cross-lane, transposed-LDS-read and LDS-DMA paths) after the coherence
     stage and before integrity, in the same way; its result nests under
-    ``"movement"``.  The order is quick, compute, formats, coherence,
-    movement, integrity.
+    ``"movement"``.
+
+    ``alu=True`` adds the ALU stage (nodeops/alu.py: the vector and scalar
+    ALUs and the transcendental consensus) after the movement stage and before
+    integrity, in the same way; its result nests under ``"alu"``.  The order
+    is quick, compute, formats, coherence, movement, alu, integrity.
     """
     if level not in PROBE_LEVELS:
         raise ValueError(f"unknown probe level {level!r} (expected one of {PROBE_LEVELS})")
-    if level == "quick" and not compute and not formats and not coherence and not movement:
+    if (level == "quick" and not compute and not formats and not coherence and not movement
+            and not alu):
         return probe_fn_for_nodeops
 
     def staged_probe(gpu) -> dict:
@@ -1014,6 +1020,15 @@ def make_probe_fn(level: str = "quick", vram_bytes: int = 0, link_bytes: int = 0
                 result["ok"] = False
                 result["msg"] = stage.get("msg", "movement probe failed")
                 return result
+        if alu:
+            from .alu import run_alu
+
+            stage = run_alu(dev, seed=seed, min_cu_fraction=alu_min_cu_fraction)
+            result["alu"] = stage
+            if not stage.get("ok"):
+                result["ok"] = False
+                result["msg"] = stage.get("msg", "alu probe failed")
+                return result
         if level == "deep":
             integrity = run_integrity(
                 dev, vram_bytes=vram_bytes, link_bytes=link_bytes, seed=seed,
@@ -1033,6 +1048,8 @@ def make_probe_fn(level: str = "quick", vram_bytes: int = 0, link_bytes: int = 0
         staged_probe.coherence = True
     if movement:
         staged_probe.movement = True
+    if alu:
+        staged_probe.alu = True
     return staged_probe
 
 
@@ -1072,6 +1089,15 @@ def _movement_argv(movement, movement_min_cu_fraction) -> list:
     return argv
 
 
+def _alu_argv(alu, alu_min_cu_fraction) -> list:
+    if not alu:
+        return []
+    argv = ["--alu"]
+    if alu_min_cu_fraction:
+        argv += ["--alu-min-cu-fraction", str(float(alu_min_cu_fraction))]
+    return argv
+
+
 def _deep_argv(level: str, vram_mib, link_mib, link_floor_gbps) -> list:
     if level == "quick":
         return []
@@ -1092,7 +1118,8 @@ def probe_via_exec(execer, node: str, gpu, argv_prefix=None, level: str = "quick
                    compute_min_cu_fraction=0, formats: bool = False,
                    formats_min_cu_fraction=0, coherence: bool = False,
                    coherence_min_cu_fraction=0, movement: bool = False,
-                   movement_min_cu_fraction=0) -> dict:
+                   movement_min_cu_fraction=0, alu: bool = False,
+                   alu_min_cu_fraction=0) -> dict:
     """Health probe through the node agent (``croagent probe --bdf``) — the
     cluster shape where controllers run off-node and reach hardware only
     through the NodeExec seam.  Returns the same dict shape as run_probe
@@ -1100,7 +1127,7 @@ def probe_via_exec(execer, node: str, gpu, argv_prefix=None, level: str = "quick
     --deep`` and the size options given; with ``compute``: as
     make_probe_fn(..., compute=True), via ``--compute``; with ``formats``:
     via ``--formats``; with ``coherence``: via ``--coherence``; with
-    ``movement``: via ``--movement``).
+    ``movement``: via ``--movement``; with ``alu``: via ``--alu``).
 
     ``argv_prefix`` wraps the command for the container-driver arm (e.g.
     ``["chroot", "/run/amdgpu-driver"]`` so the probe runs against the
@@ -1115,6 +1142,7 @@ def probe_via_exec(execer, node: str, gpu, argv_prefix=None, level: str = "quick
     argv += _formats_argv(formats, formats_min_cu_fraction)
     argv += _coherence_argv(coherence, coherence_min_cu_fraction)
     argv += _movement_argv(movement, movement_min_cu_fraction)
+    argv += _alu_argv(alu, alu_min_cu_fraction)
     rc, out, err = execer.run(node, argv, timeout=300)
     if rc != 0 and not out.strip():
         return {"ok": False, "rc": rc, "msg": err.strip() or "croagent probe failed"}
@@ -1129,7 +1157,8 @@ def make_exec_probe_fn(execer, node: str, argv_prefix_fn=None, level: str = "qui
                        compute_min_cu_fraction=0, formats: bool = False,
                        formats_min_cu_fraction=0, coherence: bool = False,
                        coherence_min_cu_fraction=0, movement: bool = False,
-                       movement_min_cu_fraction=0):
+                       movement_min_cu_fraction=0, alu: bool = False,
+                       alu_min_cu_fraction=0):
     """AmdNodeOps probe hook bound to a NodeExec (local or remote agent).
 
     ``argv_prefix_fn()`` is resolved per probe so a driver-mode change
@@ -1146,6 +1175,8 @@ def make_exec_probe_fn(execer, node: str, argv_prefix_fn=None, level: str = "qui
         stages.update(coherence=True, coherence_min_cu_fraction=coherence_min_cu_fraction)
     if movement:
         stages.update(movement=True, movement_min_cu_fraction=movement_min_cu_fraction)
+    if alu:
+        stages.update(alu=True, alu_min_cu_fraction=alu_min_cu_fraction)
 
     def probe(gpu):
         prefix = argv_prefix_fn() if argv_prefix_fn else None
